@@ -18,6 +18,11 @@ median of 10; cpu_baseline_update: the torch-CPU fp32 network oracle (oracle/net
 update's minibatch work, scaled to one update (both run before the GPU is touched).
 GPU timing: `value` = env transitions / wall time of exactly K steps between barriers; the per-step
 median from HIP events is reported beside it (warm-up 10, median of 50 = the defaults).
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only what `value` needs: set-up, W warm-up steps, the K timed
+steps, the result line.  `--full` adds everything else described above (cpu_baseline*, the kernels' own durations and
+the roofline, the "ppo" object; `--no-cpu-baseline` and `--ppo-iters` trim it).  `--dump-outputs DIR` writes the last
+timed step's rollout (a fixed seeded sample of envs) to DIR/<name>.npy, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -413,130 +418,34 @@ def ppo_bench(env, dev, world, rank, iters, strong=False):
             "mfma_pmc": pmc}
 
 
-def _free_port() -> int:
-    import socket
-
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+DUMP_BUDGET_BYTES, DUMP_SEED = 64 * 10 ** 6, 0  # --dump-outputs: all files together; the env sample's seed
 
 
-def launch_ranks(n: int) -> int:
-    """`bench.py --gpus N` run directly (no torchrun): start N fresh child processes of this script, one per
-    GPU, with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, exactly as
-    `torch.distributed.run --nproc-per-node N` would; rank 0 prints the JSON line.  This parent never
-    touches the GPU (no HIP call before or after the children), and if a rank fails the others are
-    terminated.  Returns the first non-zero exit code (0 when every rank succeeded)."""
-    import subprocess
-
-    port = str(_free_port())
-    procs = []
-    for r in range(n):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=port)
-        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
-    rc = 0
-    while procs:
-        for p in list(procs):
-            code = p.poll()
-            if code is None:
-                continue
-            procs.remove(p)
-            if code != 0 and rc == 0:
-                rc = code
-                for q in procs:
-                    q.terminate()
-        time.sleep(0.2)
-    return rc
+def dump_outputs(eng, out_dir, rank=0, world=1):
+    """--dump-outputs: what the last timed step handed its caller, the Rollout of eng.run(): per env the sequence
+    of T+1 graphs (Rollout.graph is [:, :T] of it, Rollout.next_graph [:, 1:]; nodes, edges, states, receivers,
+    senders), rewards and costs, as out_dir/<name>.npy with the Rollout's leading (env, time) dims.  The whole
+    rollout is several GB, so a fixed seeded sample of envs is written (envs.npy: their indices, ascending), as many
+    as keep all files within DUMP_BUDGET_BYTES.  float32 as computed; the int32 index fields and envs as float64."""
+    b = eng.buf
+    fields = {"nodes": b.nodes, "edges": b.edges, "states": b.states, "receivers": b.receivers, "senders": b.senders,
+              "rewards": eng.rewards, "costs": eng.costs}  # time-major: (T+1 or T, B, ...)
+    per_env = 8 + sum(x[:, 0].numel() * (4 if x.is_floating_point() else 8) for x in fields.values())
+    n_sample = min(eng.B, (DUMP_BUDGET_BYTES - 4096) // per_env)  # 4096: the .npy headers
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(eng.B, n_sample, replace=False))
+    sel = torch.as_tensor(idx, device=eng.device)
+    sfx = "" if world == 1 else f".rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"envs{sfx}.npy"), idx.astype(np.float64))
+    for name, x in fields.items():
+        a = x.index_select(1, sel).transpose(0, 1).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"),
+                np.ascontiguousarray(a, dtype=np.float32 if a.dtype.kind == "f" else np.float64))
 
 
-def main():
-    global B_PER_GPU
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)  # SURVEY.md 8(d): warm-up 10, median of 50
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--strong", action="store_true",
-                    help="strong scaling: 4096 envs (and the 16,384-sample PPO batch) in total, split over the ranks")
-    ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--ppo-iters", type=int, default=10, help="timed DGPPO collect+update iterations (0: skip)")
-    ap.add_argument("--print-rank-env", action="store_true", help=argparse.SUPPRESS)  # launcher test (CPU only)
-    args = ap.parse_args()
-
-    env_world = os.environ.get("WORLD_SIZE")
-    if env_world is None and args.gpus > 1:
-        sys.exit(launch_ranks(args.gpus))
-    world = int(env_world or "1")
-    if world != args.gpus:
-        sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; launch one rank per GPU "
-                 f"(torch.distributed.run --nproc-per-node {args.gpus}) or drop WORLD_SIZE")
-    rank = int(os.environ.get("RANK", "0"))
-    if args.print_rank_env:  # tests/test_bench_cpu.py: what each launched rank sees, before any GPU use
-        print(json.dumps({k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR",
-                                                          "MASTER_PORT")}), flush=True)
-        return
-    if args.strong:
-        if B_TOTAL_STRONG % world:
-            sys.exit(f"bench.py --strong: {B_TOTAL_STRONG} envs do not split over {world} ranks")
-        B_PER_GPU = B_TOTAL_STRONG // world
-    # CPU baselines first: forked workers must never inherit an initialised GPU context
-    cpu_env = cpu_upd = cpu_roll = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu_env = cpu_baseline()
-        cpu_roll = cpu_baseline_rollout()
-        cpu_upd = cpu_baseline_update() if args.ppo_iters > 0 else None
-
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    ndev = torch.cuda.device_count()
-    local = local % ndev if ndev > 0 else local  # identity on a full node; wraps for one-GPU rehearsals
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    if world > 1:
-        # RCCL over xGMI; DGPPO_DIST_BACKEND=gloo rehearses the multi-rank path with several ranks
-        # sharing one GPU (RCCL refuses two ranks on one device)
-        backend = os.environ.get("DGPPO_DIST_BACKEND", "nccl")
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=dev)
-        else:
-            dist.init_process_group(backend)
-
-    from dgppo_fov_amd.env import make_env
-    from dgppo_fov_amd.trainer.rollout import RolloutEngine
-
-    env = make_env(ENV_ID, N_AGENTS, num_obs=N_OBS, device=dev)
-    lanes = int(os.environ.get("DGPPO_BENCH_LANES", "1"))  # 1: states-only reset + ONE persistent rollout launch
-    eng = RolloutEngine(env, B_PER_GPU, T, dev, env_offset=rank * B_PER_GPU, lanes=lanes)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(1000 + rank)
-    eng.actions.uniform_(-1.0, 1.0, generator=gen)  # synthetic actions, resident before timing
-    use_graph = not args.no_graph
-    if use_graph:
-        eng.capture()
-    for w in range(args.warmup):
-        eng.run(key=w)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    stream = torch.cuda.current_stream(dev)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for s in range(args.steps):
-        evs[s].record(stream)
-        eng.run(key=10_000 + s)
-    evs[-1].record(stream)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
-    elapsed = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    step_ms_median = float(np.median([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]))
-
+def live_kernel_ms(env, eng, dev, use_graph, lanes):
+    """--full: the env kernels' own durations for the roofline, in runs of their own after the timed steps
+    (they overwrite the rollout buffer): (persistent rollout kernel ms per launch or None, step kernel ms)."""
     # ---- live kernel timing for the roofline (HIP events on the launch stream) ----
     stream = torch.cuda.current_stream(dev)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -596,50 +505,191 @@ def main():
         ev1.synchronize()
         kern_ms.append(ev0.elapsed_time(ev1) / n_launch)
     step_ms = float(np.median(kern_ms))
+    return roll_ms, step_ms
+
+
+def _free_port() -> int:
+    import socket
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def launch_ranks(n: int) -> int:
+    """`bench.py --gpus N` run directly (no torchrun): start N fresh child processes of this script, one per
+    GPU, with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, exactly as
+    `torch.distributed.run --nproc-per-node N` would; rank 0 prints the JSON line.  This parent never
+    touches the GPU (no HIP call before or after the children), and if a rank fails the others are
+    terminated.  Returns the first non-zero exit code (0 when every rank succeeded)."""
+    import subprocess
+
+    port = str(_free_port())
+    procs = []
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
+                   MASTER_ADDR="127.0.0.1", MASTER_PORT=port)
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
+    rc = 0
+    while procs:
+        for p in list(procs):
+            code = p.poll()
+            if code is None:
+                continue
+            procs.remove(p)
+            if code != 0 and rc == 0:
+                rc = code
+                for q in procs:
+                    q.terminate()
+        time.sleep(0.2)
+    return rc
+
+
+def main():
+    global B_PER_GPU
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=50)  # SURVEY.md 8(d): warm-up 10, median of 50
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--strong", action="store_true",
+                    help="strong scaling: 4096 envs (and the 16,384-sample PPO batch) in total, split over the ranks")
+    ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baselines, the env kernels' own "
+                         "durations (roofline) and DGPPO training iterations (ppo)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's rollout (a fixed sample of envs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--ppo-iters", type=int, default=10,
+                    help="with --full: timed DGPPO collect+update iterations (0: skip)")
+    ap.add_argument("--print-rank-env", action="store_true", help=argparse.SUPPRESS)  # launcher test (CPU only)
+    args = ap.parse_args()
+
+    env_world = os.environ.get("WORLD_SIZE")
+    if env_world is None and args.gpus > 1:
+        sys.exit(launch_ranks(args.gpus))
+    world = int(env_world or "1")
+    if world != args.gpus:
+        sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; launch one rank per GPU "
+                 f"(torch.distributed.run --nproc-per-node {args.gpus}) or drop WORLD_SIZE")
+    rank = int(os.environ.get("RANK", "0"))
+    if args.print_rank_env:  # tests/test_bench_cpu.py: what each launched rank sees, before any GPU use
+        print(json.dumps({k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR",
+                                                          "MASTER_PORT")}), flush=True)
+        return
+    if args.strong:
+        if B_TOTAL_STRONG % world:
+            sys.exit(f"bench.py --strong: {B_TOTAL_STRONG} envs do not split over {world} ranks")
+        B_PER_GPU = B_TOTAL_STRONG // world
+    # CPU baselines first: forked workers must never inherit an initialised GPU context
+    cpu_env = cpu_upd = cpu_roll = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu_env = cpu_baseline()
+        cpu_roll = cpu_baseline_rollout()
+        cpu_upd = cpu_baseline_update() if args.ppo_iters > 0 else None
+
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    ndev = torch.cuda.device_count()
+    local = local % ndev if ndev > 0 else local  # identity on a full node; wraps for one-GPU rehearsals
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if world > 1:
+        # RCCL over xGMI; DGPPO_DIST_BACKEND=gloo rehearses the multi-rank path with several ranks
+        # sharing one GPU (RCCL refuses two ranks on one device)
+        backend = os.environ.get("DGPPO_DIST_BACKEND", "nccl")
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(backend)
+
+    from dgppo_fov_amd.env import make_env
+    from dgppo_fov_amd.trainer.rollout import RolloutEngine
+
+    env = make_env(ENV_ID, N_AGENTS, num_obs=N_OBS, device=dev)
+    lanes = int(os.environ.get("DGPPO_BENCH_LANES", "1"))  # 1: states-only reset + ONE persistent rollout launch
+    eng = RolloutEngine(env, B_PER_GPU, T, dev, env_offset=rank * B_PER_GPU, lanes=lanes)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1000 + rank)
+    eng.actions.uniform_(-1.0, 1.0, generator=gen)  # synthetic actions, resident before timing
+    use_graph = not args.no_graph
+    if use_graph:
+        eng.capture()
+    for w in range(args.warmup):
+        eng.run(key=w)
+    torch.cuda.synchronize(dev)
+    if world > 1:
+        dist.barrier()
+    stream = torch.cuda.current_stream(dev)
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for s in range(args.steps):
+        evs[s].record(stream)
+        eng.run(key=10_000 + s)
+    evs[-1].record(stream)
+    torch.cuda.synchronize(dev)
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize(dev)
+    elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    step_ms_median = float(np.median([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]))
+
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
 
     env_steps = args.steps * B_PER_GPU * T * world
     value = env_steps / elapsed
-    if roll_ms is not None:  # T transitions per launch
-        bytes_per_launch = BYTES_PER_ENV_STEP * B_PER_GPU * T
-        achieved = bytes_per_launch / (roll_ms * 1e-3) / 1e9
-        kname = "wv::lidar_rollout_wave_kernel<LIDAR,SPREAD,4,3> (persistent: T=128 steps per launch)"
-    else:
-        bytes_per_launch = BYTES_PER_ENV_STEP * B_PER_GPU
-        achieved = bytes_per_launch / (step_ms * 1e-3) / 1e9
-        kname = "wv::lidar_step_wave_kernel<LIDAR,SPREAD,4,3,false>"
-    step_achieved = BYTES_PER_ENV_STEP * B_PER_GPU / (step_ms * 1e-3) / 1e9
-    traffic = read_pmc_traffic(latest_profile("env_rollout_pmc.json") if roll_ms is not None else "env_step_pmc.json")
     fused = eng.fused and lanes == 1
-    del eng, outs, cur, g_step
-    ppo = ppo_bench(env, dev, world, rank, args.ppo_iters, strong=args.strong) if args.ppo_iters > 0 else None
-    if rank == 0:
-        out = {
-            "metric": METRIC,
-            "value": round(value, 1),
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "ms_per_step_median": round(step_ms_median, 4),  # HIP events around each step, rank 0
-            "higher_is_better": True,
-            "scaling": "strong" if args.strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (Philox-sampled resets, uniform random actions in HBM)",
-            "config": {
-                "workload": f"{ENV_ID} n={N_AGENTS} obs={N_OBS} rays=32 top_k=8, {B_PER_GPU} envs/GPU"
-                            f"{f' ({B_PER_GPU * world} in total, strong scaling)' if args.strong else ''}, "
-                            f"1 step = reset + T={T} fused env steps into the (B,T+1) rollout buffer",
-                "env": ENV_ID, "num_agents": N_AGENTS, "n_obs": N_OBS, "n_env_per_gpu": B_PER_GPU, "T": T,
-                "hip_graph": use_graph, "stream_lanes": lanes, "persistent_rollout": fused,
-                "parallelism": f"dp{world} (env-sharded, no collective)",
-            },
+    out = {
+        "metric": METRIC,
+        "value": round(value, 1),
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "ms_per_step_median": round(step_ms_median, 4),  # HIP events around each step, rank 0
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (Philox-sampled resets, uniform random actions in HBM)",
+        "config": {
+            "workload": f"{ENV_ID} n={N_AGENTS} obs={N_OBS} rays=32 top_k=8, {B_PER_GPU} envs/GPU"
+                        f"{f' ({B_PER_GPU * world} in total, strong scaling)' if args.strong else ''}, "
+                        f"1 step = reset + T={T} fused env steps into the (B,T+1) rollout buffer",
+            "env": ENV_ID, "num_agents": N_AGENTS, "n_obs": N_OBS, "n_env_per_gpu": B_PER_GPU, "T": T,
+            "hip_graph": use_graph, "stream_lanes": lanes, "persistent_rollout": fused,
+            "parallelism": f"dp{world} (env-sharded, no collective)",
+        },
+        "full": args.full,
+        # whole timed region (reset + T steps, 2 env slices on 2 streams) at the per-transition bytes
+        "rollout_effective_hbm_gbs": round(value / world * BYTES_PER_ENV_STEP / 1e9, 1),
+    }
+    if args.full:
+        # everything beyond the headline figure: the kernels' own durations (roofline), DGPPO training iterations
+        roll_ms, step_ms = live_kernel_ms(env, eng, dev, use_graph, lanes)
+        if roll_ms is not None:  # T transitions per launch
+            bytes_per_launch = BYTES_PER_ENV_STEP * B_PER_GPU * T
+            achieved = bytes_per_launch / (roll_ms * 1e-3) / 1e9
+            kname = "wv::lidar_rollout_wave_kernel<LIDAR,SPREAD,4,3> (persistent: T=128 steps per launch)"
+        else:
+            bytes_per_launch = BYTES_PER_ENV_STEP * B_PER_GPU
+            achieved = bytes_per_launch / (step_ms * 1e-3) / 1e9
+            kname = "wv::lidar_step_wave_kernel<LIDAR,SPREAD,4,3,false>"
+        step_achieved = BYTES_PER_ENV_STEP * B_PER_GPU / (step_ms * 1e-3) / 1e9
+        traffic = read_pmc_traffic(latest_profile("env_rollout_pmc.json") if roll_ms is not None
+                                   else "env_step_pmc.json")
+        del eng
+        ppo = ppo_bench(env, dev, world, rank, args.ppo_iters, strong=args.strong) if args.ppo_iters > 0 else None
+        out.update({
             "env_step_kernel_us": round(step_ms * 1e3, 3),
             "env_step_kernel_gbs": round(step_achieved, 1),  # the per-step kernel the policy rollouts launch
             "env_rollout_kernel_us": None if roll_ms is None else round(roll_ms * 1e3, 2),
-            # whole timed region (reset + T steps, 2 env slices on 2 streams) at the per-transition bytes
-            "rollout_effective_hbm_gbs": round(value / world * BYTES_PER_ENV_STEP / 1e9, 1),
             "ppo_updates_per_s": None if ppo is None else ppo["updates_per_s"],
             "ppo": ppo,
             "roofline": {
@@ -655,7 +705,8 @@ def main():
             "cpu_baseline": cpu_env,
             "cpu_baseline_update": cpu_upd,
             "cpu_baseline_rollout": cpu_roll,
-        }
+        })
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
