@@ -125,6 +125,20 @@ class EnvResetIO(ctypes.Structure):
     ]
 
 
+class EnvGraphIO(ctypes.Structure):  # dgppo_env_graph_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("goal", c_f32p), ("goal_stride", ctypes.c_int64),
+        ("third", c_f32p), ("third_stride", ctypes.c_int64),
+        ("ray_dirs", c_f32p),
+        ("nodes", c_f32p), ("nodes_stride", ctypes.c_int64),
+        ("edges", c_f32p), ("edges_stride", ctypes.c_int64),
+        ("out_states", c_f32p), ("out_states_stride", ctypes.c_int64),
+        ("receivers", c_f32p), ("senders", c_f32p), ("edge_index_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32),
+    ]
+
+
 class EnvRolloutIO(ctypes.Structure):
     _fields_ = [
         ("step", EnvStepIO),
@@ -289,6 +303,8 @@ SIGNATURES = {
     "dgppo_env_reset": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvResetIO), ctypes.c_void_p]),
     "dgppo_env_reset_states": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvResetIO), ctypes.c_void_p]),
     "dgppo_env_rollout": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvRolloutIO), ctypes.c_void_p]),
+    "dgppo_env_get_graph": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphIO), ctypes.c_void_p]),
+    "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_gemm_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs)]),
     "dgppo_gemm_wgrad_grouped_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs), ctypes.c_int]),
     "dgppo_gemm_wgrad_grouped": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_int, c_f32p, ctypes.c_void_p]),

@@ -1281,11 +1281,15 @@ __device__ __forceinline__ float3 wave_action(const dgppo_env_step_io& io, int64
 }
 
 // (pre: LOAD = false only — this step's raw actions, loaded by the caller one step ahead)
-template <int ENGINE, int GOAL, int SD, int O, bool REBUILD, bool LOAD, int WPG = 4>
+// SPLIT (REBUILD + LOAD only, dgppo_env_get_graph): io.states holds the agent rows alone and the goal rows come
+// from goal_rows (per-env stride goal_stride); there are no current hits to read.
+template <int ENGINE, int GOAL, int SD, int O, bool REBUILD, bool LOAD, int WPG = 4, bool SPLIT = false>
 __device__ __forceinline__ void wave_body(const dgppo_env_cfg& cfg, const dgppo_env_step_io& io, float* smem,
                                           int* wg_items, float3 pre = make_float3(0.0f, 0.0f, 0.0f),
-                                          EnvStamps* stamps = nullptr, const WaveConst<O>* pc = nullptr) {
+                                          EnvStamps* stamps = nullptr, const WaveConst<O>* pc = nullptr,
+                                          const float* goal_rows = nullptr, int64_t goal_stride = 0) {
   (void)stamps;
+  static_assert(!SPLIT || (REBUILD && LOAD), "split agent / goal rows: the graph of given states only");
   static_assert(O >= 1 && O <= 4, "obstacle records are staged by one load per lane");
   // LidarOmniTarget (SD 7, own goals): omni dynamics, 5 costs, 10-wide edges; same LiDAR and graph rows
   constexpr bool OMNI = ENGINE == DGPPO_ENGINE_OMNI;
@@ -1324,10 +1328,18 @@ __device__ __forceinline__ void wave_body(const dgppo_env_cfg& cfg, const dgppo_
   if constexpr (LOAD) {
     const float* st = io.states + env * io.states_stride;
     const float* ob = io.obstacles + env * io.obstacles_stride;
-    const float cv0 = st[lane];
     const int xsl = 64 + (lane < XS ? lane : XS - 1);
-    const float cv1 = XS > 0 ? st[xsl] : 0.0f;
-    hcx = st[(16 + lane) * SD + 0], hcy = st[(16 + lane) * SD + 1];
+    float cv0, cv1;
+    if constexpr (SPLIT) {  // element e of [agent rows | goal rows]
+      const float* gl = goal_rows + env * goal_stride;
+      cv0 = lane < NA * SD ? st[lane] : gl[lane - NA * SD];
+      cv1 = XS > 0 ? (xsl < NA * SD ? st[xsl] : gl[xsl - NA * SD]) : 0.0f;
+      hcx = 0.0f, hcy = 0.0f;
+    } else {
+      cv0 = st[lane];
+      cv1 = XS > 0 ? st[xsl] : 0.0f;
+      hcx = st[(16 + lane) * SD + 0], hcy = st[(16 + lane) * SD + 1];
+    }
     const float obv = ob[lane < O * DGPPO_OBST_FIELDS ? lane : 0];
     const float rdv = io.ray_dirs[lane];
     // unconditional LDS stores: a store under a lane predicate lets the compiler sink its global load
@@ -1957,6 +1969,17 @@ __global__ __launch_bounds__(256) void lidar_step_wave_kernel(dgppo_env_cfg cfg,
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int wg_items[4];
   wave_body<ENGINE, GOAL, SD, O, REBUILD, true>(cfg, io, smem, wg_items);
+}
+
+// The graph of caller-given states (dgppo_env_get_graph): the REBUILD step above with the agent rows read from
+// io.states and the goal rows from `goal`.
+template <int ENGINE, int GOAL, int SD, int O>
+__global__ __launch_bounds__(256) void lidar_graph_wave_kernel(dgppo_env_cfg cfg, dgppo_env_step_io io,
+                                                               const float* goal, int64_t goal_stride) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ int wg_items[4];
+  wave_body<ENGINE, GOAL, SD, O, true, true, 4, true>(cfg, io, smem, wg_items, make_float3(0.0f, 0.0f, 0.0f), nullptr,
+                                                      nullptr, goal, goal_stride);
 }
 
 constexpr int kRolloutActFloats = 16 * NA * 3;  // per wave: a 16-step action chunk (3 action floats max)
@@ -2719,6 +2742,40 @@ __device__ void node_goal_rng_wave(Rng& rng, const float* tab, float side, int n
   rng.count = count;
 }
 
+// The graph half shared by env_reset_kernel and env_graph_kernel: with the agent rows staged at cv.nxt, the goal rows
+// (then the MPE obstacle rows) after the n agent rows of cv.cur and the Lidar records at cv.obst, and a barrier behind
+// them, ray-cast (Lidar) and write env's graph.  IO: dgppo_env_reset_io or dgppo_env_graph_io (same output fields).
+template <int ENGINE, int GOAL, int SD, int BLOCK, class IO>
+__device__ __forceinline__ void graph_of_staged_rows(const dgppo_env_cfg& cfg, const IO& io, const Dims<0, -1, 0, 0>& d,
+                                                     const Carve& cv, float* lds, int64_t env) {
+  const bool mpe = ENGINE == DGPPO_ENGINE_MPE;
+  const int n = d.n, O = d.O, k = d.k;
+  const bool lidar = !mpe && O > 0;
+  const int tid = threadIdx.x;
+  const float* nxt = lds + cv.nxt;
+  const float* goal = lds + cv.cur + n * SD;
+  const float* third = lds + cv.cur + 2 * n * SD;  // MPE obstacle states
+  if (lidar) {
+    for (int i = tid; i < n; i += BLOCK) agent_is_inside(O, lds, cv, SD, i);
+    stage_edge_vectors(O, lds, cv, tid, BLOCK);
+    __syncthreads();
+    lidar_scan<SD>(d, io.ray_dirs, lds, cv, tid, BLOCK);
+    __syncthreads();
+  }
+  GraphOut out;
+  out.nodes = io.nodes + env * io.nodes_stride;
+  out.edges = io.edges + env * io.edges_stride;
+  out.states = io.out_states + env * io.out_states_stride;
+  out.recv = io.receivers + env * io.edge_index_stride;
+  out.send = io.senders + env * io.edge_index_stride;
+  if constexpr (ENGINE == DGPPO_ENGINE_OMNI) {
+    write_graph_omni(cfg, n, k, lidar, nxt, goal, lds + cv.hits, out, tid, BLOCK);
+  } else {
+    const bool vec4 = ((io.edges_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(io.edges) & 15) == 0);
+    write_graph<ENGINE, GOAL, SD>(cfg, d, nxt, goal, mpe ? third : lds + cv.hits, out, vec4, tid, BLOCK);
+  }
+}
+
 template <int ENGINE, int GOAL, int SD, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void env_reset_kernel(dgppo_env_cfg cfg, dgppo_env_reset_io io, int states_only) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -2835,24 +2892,42 @@ __global__ __launch_bounds__(BLOCK) void env_reset_kernel(dgppo_env_cfg cfg, dgp
   if (lidar) {
     float* ob = io.obstacles + env * io.obstacles_stride;
     for (int idx = tid; idx < O * DGPPO_OBST_FIELDS; idx += BLOCK) ob[idx] = obst[idx];
-    for (int i = tid; i < n; i += BLOCK) agent_is_inside(O, lds, cv, SD, i);
-    stage_edge_vectors(O, lds, cv, tid, BLOCK);
-    __syncthreads();
-    lidar_scan<SD>(d, io.ray_dirs, lds, cv, tid, BLOCK);
-    __syncthreads();
   }
-  GraphOut out;
-  out.nodes = io.nodes + env * io.nodes_stride;
-  out.edges = io.edges + env * io.edges_stride;
-  out.states = io.out_states + env * io.out_states_stride;
-  out.recv = io.receivers + env * io.edge_index_stride;
-  out.send = io.senders + env * io.edge_index_stride;
-  if constexpr (ENGINE == DGPPO_ENGINE_OMNI) {
-    write_graph_omni(cfg, n, k, lidar, nxt, goal, lds + cv.hits, out, tid, BLOCK);
-  } else {
-    const bool vec4 = ((io.edges_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(io.edges) & 15) == 0);
-    write_graph<ENGINE, GOAL, SD>(cfg, d, nxt, goal, mpe ? third : lds + cv.hits, out, vec4, tid, BLOCK);
+  graph_of_staged_rows<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
+}
+
+// The graph of caller-given states (dgppo_env_get_graph; the reference's get_lidar_data + get_graph,
+// lidar_env/base.py:126-140 / 227-271, mpe/base.py:211-241): the reset kernel's graph half with the agent, goal
+// and obstacle rows loaded instead of sampled.  No clipping; the sampler's candidate table is not carved.
+template <int ENGINE, int GOAL, int SD, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void env_graph_kernel(dgppo_env_cfg cfg, dgppo_env_graph_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const bool mpe = ENGINE == DGPPO_ENGINE_MPE;
+  const Dims<0, -1, 0, 0> d(cfg);
+  const int n = d.n, O = d.O, k = d.k;
+  const bool lidar = !mpe && O > 0;
+  const Carve cv(n, SD, O, cfg.n_rays, k, !mpe);
+  const int tid = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  float* nxt = lds + cv.nxt;
+  float* goal = lds + cv.cur + n * SD;
+  float* third = lds + cv.cur + 2 * n * SD;  // MPE obstacle states
+  const float* ag = io.agent + env * io.agent_stride;
+  const float* gl = io.goal + env * io.goal_stride;
+  for (int idx = tid; idx < n * SD; idx += BLOCK) {
+    nxt[idx] = ag[idx];
+    goal[idx] = gl[idx];
   }
+  if (mpe && O > 0) {
+    const float* ob = io.third + env * io.third_stride;
+    for (int idx = tid; idx < O * SD; idx += BLOCK) third[idx] = ob[idx];
+  }
+  if (lidar) {
+    const float* ob = io.third + env * io.third_stride;
+    for (int idx = tid; idx < O * DGPPO_OBST_FIELDS; idx += BLOCK) lds[cv.obst + idx] = ob[idx];
+  }
+  __syncthreads();
+  graph_of_staged_rows<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
 }
 
 // ---- reference env variants ------------------------------------------------------------------
@@ -3155,6 +3230,34 @@ __device__ __forceinline__ float min_dist_row(const float* p, int n, int i) {  /
   return md;
 }
 
+// The graph half shared by reset_kernel and graph_kernel (rows staged as graph_of_staged_rows wants them, with
+// n_goals goal node rows): ray cast (LidarLine) and write_graph_var.
+template <int ENGINE, class IO>
+__device__ __forceinline__ void graph_of_staged_rows_var(const dgppo_env_cfg& cfg, const IO& io,
+                                                         const Dims<0, -1, 0, 0>& d, const Carve& cv, float* lds,
+                                                         int64_t env) {
+  constexpr int SD = 4;
+  constexpr bool mpe = ENGINE == DGPPO_ENGINE_MPE;
+  const int n = d.n, O = d.O, t0 = n + cfg.n_goals;
+  const bool lidar = !mpe && O > 0;
+  const int tid = threadIdx.x;
+  if (lidar) {
+    for (int i = tid; i < n; i += kT) agent_is_inside(O, lds, cv, SD, i);
+    stage_edge_vectors(O, lds, cv, tid, kT);
+    __syncthreads();
+    lidar_scan<SD>(d, io.ray_dirs, lds, cv, tid, kT);
+    __syncthreads();
+  }
+  GraphOut out;
+  out.nodes = io.nodes + env * io.nodes_stride;
+  out.edges = io.edges + env * io.edges_stride;
+  out.states = io.out_states + env * io.out_states_stride;
+  out.recv = io.receivers + env * io.edge_index_stride;
+  out.send = io.senders + env * io.edge_index_stride;
+  write_graph_var(cfg, mpe, lidar, lds + cv.nxt, lds + cv.cur + n * SD, mpe ? lds + cv.cur + t0 * SD : lds + cv.hits,
+                  out, tid, kT);
+}
+
 template <int ENGINE>
 __global__ __launch_bounds__(kT) void reset_kernel(dgppo_env_cfg cfg, dgppo_env_reset_io io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -3272,19 +3375,39 @@ __global__ __launch_bounds__(kT) void reset_kernel(dgppo_env_cfg cfg, dgppo_env_
   if (lidar) {
     float* ob = io.obstacles + env * io.obstacles_stride;
     for (int idx = tid; idx < O * DGPPO_OBST_FIELDS; idx += kT) ob[idx] = lds[cv.obst + idx];
-    for (int i = tid; i < n; i += kT) agent_is_inside(O, lds, cv, SD, i);
-    stage_edge_vectors(O, lds, cv, tid, kT);
-    __syncthreads();
-    lidar_scan<SD>(d, io.ray_dirs, lds, cv, tid, kT);
-    __syncthreads();
   }
-  GraphOut out;
-  out.nodes = io.nodes + env * io.nodes_stride;
-  out.edges = io.edges + env * io.edges_stride;
-  out.states = io.out_states + env * io.out_states_stride;
-  out.recv = io.receivers + env * io.edge_index_stride;
-  out.send = io.senders + env * io.edge_index_stride;
-  write_graph_var(cfg, mpe, lidar, lds + cv.nxt, grow, mpe ? obs : lds + cv.hits, out, tid, kT);
+  graph_of_staged_rows_var<ENGINE>(cfg, io, d, cv, lds, env);
+}
+
+// The graph of caller-given states for the variants (dgppo_env_get_graph): reset_kernel's graph half with the
+// agent rows, the goal NODE rows (landmarks) and the obstacles loaded instead of sampled.
+template <int ENGINE>
+__global__ __launch_bounds__(kT) void graph_kernel(dgppo_env_cfg cfg, dgppo_env_graph_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int SD = 4;
+  constexpr bool mpe = ENGINE == DGPPO_ENGINE_MPE;
+  const Dims<0, -1, 0, 0> d(cfg);
+  const int n = d.n, O = d.O, ng = cfg.n_goals, t0 = n + ng;
+  const bool lidar = !mpe && O > 0;
+  const Carve cv(n, SD, O, d.R, d.k, !mpe);
+  float* grow = lds + cv.cur + n * SD;  // goal node rows
+  float* obs = lds + cv.cur + t0 * SD;  // MPE obstacle rows
+  const int tid = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  const float* ag = io.agent + env * io.agent_stride;
+  const float* gl = io.goal + env * io.goal_stride;
+  for (int idx = tid; idx < n * SD; idx += kT) lds[cv.nxt + idx] = ag[idx];
+  for (int idx = tid; idx < ng * SD; idx += kT) grow[idx] = gl[idx];
+  if (mpe && O > 0) {
+    const float* ob = io.third + env * io.third_stride;
+    for (int idx = tid; idx < O * SD; idx += kT) obs[idx] = ob[idx];
+  }
+  if (lidar) {
+    const float* ob = io.third + env * io.third_stride;
+    for (int idx = tid; idx < O * DGPPO_OBST_FIELDS; idx += kT) lds[cv.obst + idx] = ob[idx];
+  }
+  __syncthreads();
+  graph_of_staged_rows_var<ENGINE>(cfg, io, d, cv, lds, env);
 }
 }  // namespace var
 
@@ -3434,6 +3557,34 @@ static void dispatch_reset(const dgppo_env_cfg& c, const dgppo_env_reset_io& io,
     default:
       return spread ? dispatch_reset_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s, so)
                     : dispatch_reset_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s, so);
+  }
+}
+
+template <int ENGINE, int GOAL, int SD>
+static void dispatch_graph_sized(const dgppo_env_cfg& c, const dgppo_env_graph_io& io, size_t shmem, hipStream_t s) {
+  const dim3 grid((unsigned)io.n_env);
+  if (ENGINE == DGPPO_ENGINE_MPE)  // no ray cast: one wave
+    hipLaunchKernelGGL((env_graph_kernel<ENGINE, GOAL, SD, 64>), grid, dim3(64), shmem, s, c, io);
+  else if (c.n_agents * c.n_rays >= 256)
+    hipLaunchKernelGGL((env_graph_kernel<ENGINE, GOAL, SD, 256>), grid, dim3(256), shmem, s, c, io);
+  else
+    hipLaunchKernelGGL((env_graph_kernel<ENGINE, GOAL, SD, 128>), grid, dim3(128), shmem, s, c, io);
+}
+
+static void dispatch_graph(const dgppo_env_cfg& c, const dgppo_env_graph_io& io, size_t shmem, hipStream_t s) {
+  const bool spread = c.goal_mode == DGPPO_GOAL_SPREAD;
+  switch (c.engine) {
+    case DGPPO_ENGINE_MPE:
+      return spread ? dispatch_graph_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s)
+                    : dispatch_graph_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s);
+    case DGPPO_ENGINE_BICYCLE:
+      return spread ? dispatch_graph_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(c, io, shmem, s)
+                    : dispatch_graph_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(c, io, shmem, s);
+    case DGPPO_ENGINE_OMNI:
+      return dispatch_graph_sized<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>(c, io, shmem, s);
+    default:
+      return spread ? dispatch_graph_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s)
+                    : dispatch_graph_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s);
   }
 }
 
@@ -3845,4 +3996,100 @@ extern "C" int dgppo_env_reset(const dgppo_env_cfg* cfg, const dgppo_env_reset_i
   st.n_env = io->n_env;
   launch_rebuild(cfg, st, s);
   return (int)hipGetLastError();
+}
+
+// the wave shape's graph of given states: lidar_graph_wave_kernel, launched as launch_rebuild launches the REBUILD step
+template <int ENGINE, int GOAL, int SD>
+static void launch_graph_wave(const dgppo_env_cfg& c, const dgppo_env_step_io& st, const dgppo_env_graph_io& io,
+                              hipStream_t s) {
+  const dim3 grid((unsigned)((st.n_env + 3) / 4)), block(256);
+  const size_t sh = 4 * sizeof(float) * wv::Carve<SD, 3>::total;
+  hipLaunchKernelGGL((wv::lidar_graph_wave_kernel<ENGINE, GOAL, SD, 3>), grid, block, sh, s, c, st, io.goal,
+                     io.goal_stride);
+}
+
+extern "C" int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_graph_io* io, void* stream) {
+  if (validate(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (vmas::is_vmas(cfg)) return DGPPO_EINVAL;  // the VMAS record carries contact-physics state
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->goal || !io->nodes || !io->edges || !io->out_states || !io->receivers || !io->senders)
+    return DGPPO_EINVAL;
+  const bool mpe = cfg->engine == DGPPO_ENGINE_MPE;
+  const bool lidar = !mpe && cfg->n_obs > 0;
+  if (cfg->n_obs > 0 && !io->third) return DGPPO_EINVAL;
+  if (lidar && !io->ray_dirs) return DGPPO_EINVAL;
+  const hipStream_t s = (hipStream_t)stream;
+  if (cfg->variant != DGPPO_VARIANT_NONE) {
+    const size_t sh = var::lds_floats(*cfg) * sizeof(float);
+    if (sh > 64 * 1024) return DGPPO_EINVAL;
+    if (mpe)
+      hipLaunchKernelGGL(var::graph_kernel<DGPPO_ENGINE_MPE>, dim3((unsigned)io->n_env), dim3(var::kT), sh, s, *cfg,
+                         *io);
+    else
+      hipLaunchKernelGGL(var::graph_kernel<DGPPO_ENGINE_LIDAR>, dim3((unsigned)io->n_env), dim3(var::kT), sh, s, *cfg,
+                         *io);
+    return (int)hipGetLastError();
+  }
+  if (wave_config(cfg, io->edges, io->edges_stride, 0, io->out_states, io->out_states_stride, 0)) {
+    dgppo_env_step_io st{};
+    st.states = io->agent;  // agent rows only (goal rows: io->goal)
+    st.states_stride = io->agent_stride;
+    st.obstacles = io->third;
+    st.obstacles_stride = io->third_stride;
+    st.action = io->agent;  // read, never used in REBUILD
+    st.action_stride = io->agent_stride;
+    st.ray_dirs = io->ray_dirs;
+    st.nodes = io->nodes;
+    st.nodes_stride = io->nodes_stride;
+    st.edges = io->edges;
+    st.edges_stride = io->edges_stride;
+    st.out_states = io->out_states;
+    st.out_states_stride = io->out_states_stride;
+    st.receivers = io->receivers;
+    st.senders = io->senders;
+    st.edge_index_stride = io->edge_index_stride;
+    st.n_env = io->n_env;
+    const bool spread = cfg->goal_mode == DGPPO_GOAL_SPREAD;
+    if (cfg->engine == DGPPO_ENGINE_OMNI) launch_graph_wave<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>(*cfg, st, *io, s);
+    else if (cfg->engine == DGPPO_ENGINE_BICYCLE && spread) launch_graph_wave<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(*cfg, st, *io, s);
+    else if (cfg->engine == DGPPO_ENGINE_BICYCLE) launch_graph_wave<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(*cfg, st, *io, s);
+    else if (spread) launch_graph_wave<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(*cfg, st, *io, s);
+    else launch_graph_wave<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(*cfg, st, *io, s);
+    return (int)hipGetLastError();
+  }
+  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k, !mpe);
+  const size_t shmem = (size_t)cv.total * sizeof(float);
+  if (shmem > 64 * 1024) return DGPPO_EINVAL;
+  dispatch_graph(*cfg, *io, shmem, s);
+  return (int)hipGetLastError();
+}
+
+// Rectangle.create (env/obstacle.py:39-56) on the host: the device make_rectangle's arithmetic, term for term
+extern "C" int dgppo_make_rectangles(int64_t count, const float* center, const float* width, const float* height,
+                                     const float* theta, float* out) {
+  if (count < 0) return DGPPO_EINVAL;
+  if (count == 0) return 0;
+  if (!center || !width || !height || !theta || !out) return DGPPO_EINVAL;
+  for (int64_t i = 0; i < count; ++i) {
+    float* rec = out + i * DGPPO_OBST_FIELDS;
+    const float cx = center[2 * i], cy = center[2 * i + 1], w = width[i], h = height[i], th = theta[i];
+    float s, c;
+    sincos32(th, &s, &c);
+    const float hw = w / 2.0f, hh = h / 2.0f;
+    const float bx[4] = {hw, -hw, -hw, hw};
+    const float by[4] = {hh, hh, -hh, -hh};
+    rec[0] = cx;
+    rec[1] = cy;
+    rec[2] = w;
+    rec[3] = h;
+    rec[4] = th;
+    rec[5] = c;
+    rec[6] = s;
+    rec[7] = 0.0f;
+    for (int p = 0; p < 4; ++p) {
+      rec[8 + 2 * p] = (c * bx[p] + (-s) * by[p]) + cx;
+      rec[9 + 2 * p] = (s * bx[p] + c * by[p]) + cy;
+    }
+  }
+  return 0;
 }

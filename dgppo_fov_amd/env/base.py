@@ -359,6 +359,82 @@ class MultiAgentEnv(ABC):
                                  out.nodes, out.edges, out.states, out.receivers, out.senders, reward, cost)
         return self._assemble(out.nodes, out.edges, out.states, out.receivers, out.senders, ob)
 
+    # ---- graphs of caller-given states ------------------------------------------------------------
+    def _third_name(self) -> str:
+        return "obstacle" if self._obstacle_fields() > 0 else "obs"
+
+    def state_rows(self, state, what: str = "get_graph: state"):
+        """Check an env state tuple's shapes and return (agent (B, n, sd), goal (B, n_goal_rows, sd), third, B), third
+        = the (B, O, F) obstacle tensor the graph kernel reads (None when n_obs == 0): the Lidar records (F = 16; a
+        Rectangle or its packed tensor) or the MPE obstacle states (F = 4).  A mismatch raises a ValueError naming the
+        field as `what`.<field>."""
+        if not isinstance(state, tuple) or len(state) < 2:
+            raise ValueError(f"{what} must be the env's (agent, goal, {self._third_name()}) state tuple")
+        agent, goal = state[0], state[1]
+        n, sd = self._num_agents, self.state_dim
+        for name, t, rows in (("agent", agent, n), ("goal", goal, self.num_goals)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (rows, sd):
+                got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{what}.{name} must be (B, {rows}, {sd}), got {got}")
+        B = int(agent.shape[0])
+        if goal.shape[0] != B:
+            raise ValueError(f"{what}.goal must be ({B}, {self.num_goals}, {sd}), got {tuple(goal.shape)}")
+        third = None
+        if self.n_obs > 0:
+            third = state[2] if len(state) > 2 else None
+            third = getattr(third, "packed", third)
+            fields = self._obstacle_fields() or sd
+            if not isinstance(third, torch.Tensor) or tuple(third.shape) != (B, self.n_obs, fields):
+                got = tuple(third.shape) if isinstance(third, torch.Tensor) else type(third).__name__
+                raise ValueError(f"{what}.{self._third_name()} must be ({B}, {self.n_obs}, {fields}), got {got}")
+        return agent, goal, third, B
+
+    def get_graph(self, state, out: Optional[GraphsTuple] = None) -> GraphsTuple:
+        """Batched `vmap(env.get_graph)` with get_lidar_data (dgppo/env/base.py:137, lidar_env/base.py:227-271,
+        mpe/base.py:211-241): the graph of the caller's own state, one HIP launch (torch.ops.dgppo.env_get_graph).
+
+        `state` is this env's state tuple with one leading env axis: (agent (B, n, sd), goal (B, n_goal_rows, sd),
+        obstacle), the obstacle a Rectangle / packed (B, O, 16) tensor (Lidar), the (B, O, 4) obstacle states (MPE),
+        or None when n_obs == 0.  `graph.env_states` of any graph of this env is a valid argument.  Nothing is
+        clipped.  The returned graph carries the obstacles, so `env.step(env.get_graph(s), a)` works."""
+        agent, goal, third, B = self.state_rows(state)
+        dev = agent.device if out is None else out.nodes.device
+        _lib.require_gpu(dev, "env.get_graph")
+        _lib.require_gpu(agent.device, "env.get_graph")
+
+        def rows_of(name, t):  # fp32 on the graph's device, rows contiguous (views of a graph's states pass as they are)
+            if t.device != dev:
+                raise ValueError(f"get_graph: state.{name} is on {t.device}, the graph on {dev}")
+            t = t if t.dtype == torch.float32 else t.float()
+            return t if t.stride(-1) == 1 and t.stride(-2) == t.shape[-1] else t.contiguous()
+
+        agent, goal = rows_of("agent", agent), rows_of("goal", goal)
+        if third is not None:
+            third = rows_of(self._third_name(), third)
+        g = self.empty_graph((B,), dev) if out is None else out
+        if g.states.dim() != 3 or g.states.shape[0] != B:
+            raise ValueError(f"get_graph: out must hold {B} graphs")
+        torch.ops.dgppo.env_get_graph(self._cfg_handle, agent, goal, third, self._ray_table(dev), g.nodes, g.edges,
+                                      g.states, g.receivers, g.senders)
+        return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders,
+                              third if self._obstacle_fields() > 0 else None)
+
+    def get_lidar_data(self, agent_states: torch.Tensor, obstacles) -> torch.Tensor:
+        """Batched get_lidar_data (lidar_env/base.py:126-140): (B, n, top_k, 2) hit points of the agents at
+        `agent_states` (B, n, sd) among `obstacles` -- the hit rows of that state's graph."""
+        if self._obstacle_fields() == 0 or self.n_obs == 0:
+            raise ValueError("get_lidar_data: this env has no LiDAR")
+        if not isinstance(agent_states, torch.Tensor) or agent_states.dim() != 3:
+            raise ValueError(f"get_lidar_data: agent_states must be (B, {self._num_agents}, {self.state_dim})")
+        n, ng, k = self._num_agents, self.num_goals, int(self._params["top_k_rays"])
+        goal = agent_states.new_zeros((agent_states.shape[0], ng, self.state_dim))
+        g = self.get_graph((agent_states, goal, obstacles))
+        return g.states[:, n + ng:n + ng + n * k, :2].reshape(-1, n, k, 2)
+
+    def get_reward(self, graph: GraphsTuple, action: torch.Tensor) -> torch.Tensor:
+        """Reward (B,) of taking `action` in `graph` (lidar_spread.py:35-52, ...): the step kernel evaluates it."""
+        return self.step(graph, action).reward
+
     def _obstacles_of(self, graph: GraphsTuple) -> Optional[torch.Tensor]:
         return None
 

@@ -2,10 +2,13 @@
 
 Record layout (include/dgppo_hip.h, DGPPO_OBST_FIELDS):
     [cx, cy, width, height, theta, cos(theta), sin(theta), type, p0x, p0y, p1x, p1y, p2x, p2y, p3x, p3y]
-`Rectangle` exposes the reference's field names as views of that record (no copies); the
-rectangles themselves are created on the GPU by the reset kernel (Rectangle.create semantics).
+`Rectangle` exposes the reference's field names as views of that record (no copies); the reset kernels
+create the rectangles on the GPU, `Rectangle.create` builds them on the host with the same arithmetic
+(dgppo_make_rectangles) for scenes of the caller's own.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -18,6 +21,29 @@ class Rectangle:
     def __init__(self, packed: torch.Tensor):
         assert packed.shape[-1] == OBST_FIELDS
         self.packed = packed
+
+    @classmethod
+    def create(cls, center, width, height, theta) -> "Rectangle":
+        """Rectangle.create (dgppo/env/obstacle.py:39-56), batched: center (..., 2), width / height / theta (...)
+        -> packed records (..., 16) on the tensors' device.  Computed on the host by dgppo_make_rectangles (the
+        reset kernels' fp32 sin / cos and operation order), then copied to the device once."""
+        from .. import _lib
+
+        center = torch.as_tensor(center, dtype=torch.float32)
+        if center.dim() < 1 or center.shape[-1] != 2:
+            raise ValueError(f"Rectangle.create: center must be (..., 2), got {tuple(center.shape)}")
+        dev, shape = center.device, tuple(center.shape[:-1])
+        host = [center.detach().cpu().contiguous()]
+        for name, t in (("width", width), ("height", height), ("theta", theta)):
+            t = torch.as_tensor(t, dtype=torch.float32)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"Rectangle.create: {name} must be {shape}, got {tuple(t.shape)}")
+            host.append(t.detach().cpu().contiguous())
+        out = torch.empty(shape + (OBST_FIELDS,), dtype=torch.float32)
+        count = out.numel() // OBST_FIELDS
+        _lib.check(_lib.load().dgppo_make_rectangles(count, *(ctypes.c_void_p(t.data_ptr()) for t in host),
+                                                     ctypes.c_void_p(out.data_ptr())), "dgppo_make_rectangles")
+        return cls(out.to(dev))
 
     @property
     def type(self):

@@ -130,6 +130,10 @@ class VMASEnv(MultiAgentEnv):
         g = super()._assemble(nodes, edges, states, recv, send, obstacles)
         return g._replace(env_states=self._env_states(states, obstacles, nodes))
 
+    def get_graph(self, state, out=None) -> GraphsTuple:
+        raise NotImplementedError("VMAS envs: get_graph of given states is not supported (the env record carries "
+                                  "contact-physics state); use reset / step")
+
     def _obstacles_of(self, graph: GraphsTuple) -> torch.Tensor:
         rec = graph.env_states.record if graph.env_states is not None else None
         if rec is None:

@@ -11,6 +11,7 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::env_step       dgppo_env_step       vmap(env.step)       lidar_env/base.py:151-174, mpe/base.py:137-158
   dgppo::env_reset_states dgppo_env_reset_states  the sampling half of env_reset (no graph)
   dgppo::env_rollout    dgppo_env_rollout    lax.scan of env.step over T given actions, trainer/utils.py:45-55
+  dgppo::env_get_graph  dgppo_env_get_graph  vmap(env.get_graph)  lidar_env/base.py:126-140, 227-271, mpe/base.py:211-241
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
   dgppo::gnn_attn_bwd   dgppo_gnn_attn_bwd   its gradient (the jax.grad of update_Vl / update_policy)
   dgppo::gae            dgppo_gae            compute_dec_ocp_gae, algo/utils.py:11-79
@@ -205,6 +206,33 @@ def env_rollout(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor], acti
 @env_rollout.register_fake
 def _env_rollout_fake(cfg, rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders,
                       reward, cost) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::env_get_graph", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
+def env_get_graph(cfg: int, agent: Tensor, goal: Tensor, third: Optional[Tensor], ray_dirs: Tensor, nodes: Tensor,
+                  edges: Tensor, states: Tensor, receivers: Tensor, senders: Tensor) -> None:
+    """The graph of caller-given states for B envs: agent (B, n, sd), goal (B, n_goal_rows, sd) and `third` (the
+    Lidar obstacle records (B, O, 16) / the MPE obstacle states (B, O, 4); None when n_obs == 0) -> the graph rows a
+    reset writes.  Nothing is clipped.  Per-env strides are free; the trailing dims must be contiguous."""
+    _lib.require_gpu(states.device, "dgppo::env_get_graph")
+    io = _lib.EnvGraphIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.goal, io.goal_stride = _p(goal), _stride(goal, 2)
+    io.third, io.third_stride = _p(third), (_stride(third, 2) if third is not None else 0)
+    io.ray_dirs = _p(ray_dirs)
+    io.nodes, io.nodes_stride = _p(nodes), _stride(nodes, 2)
+    io.edges, io.edges_stride = _p(edges), _stride(edges, 2)
+    io.out_states, io.out_states_stride = _p(states), _stride(states, 2)
+    io.receivers, io.senders = _p(receivers), _p(senders)
+    io.edge_index_stride = _stride(receivers, 1)
+    io.n_env = int(agent.shape[0])
+    _lib.check(_lib.load().dgppo_env_get_graph(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
+               "dgppo_env_get_graph")
+
+
+@env_get_graph.register_fake
+def _env_get_graph_fake(cfg, agent, goal, third, ray_dirs, nodes, edges, states, receivers, senders) -> None:
     return None
 
 

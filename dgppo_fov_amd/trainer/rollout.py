@@ -31,7 +31,7 @@ class RolloutEngine:
     MODE_RANDOM, MODE_SAMPLE, MODE_DET = -1, 1, 0
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
-                 actor=None, mode: int = -1, lanes: int = 1, fused: bool = True):
+                 actor=None, mode: int = -1, lanes: int = 1, fused: bool = True, init_state=None):
         """actor: an ActorNet (or None); mode: MODE_SAMPLE (stochastic policy, sample_action),
         MODE_DET (deterministic policy, get_action) or MODE_RANDOM (keep `self.actions` as given).
         lanes: split the envs into that many contiguous slices, each running its T (act, step) pairs
@@ -40,7 +40,11 @@ class RolloutEngine:
         this needs the fused policy step (it reads only the prepared query-key workspace); the T
         sampling-noise tensors are drawn up front with the same Philox stream ids.
         fused: an env-only (MODE_RANDOM, one lane) rollout runs as a states-only reset plus one persistent
-        dgppo_env_rollout launch for all T steps (else reset + T step launches; identical results)."""
+        dgppo_env_rollout launch for all T steps (else reset + T step launches; identical results).
+        init_state: the env's state tuple (agent, goal, obstacle) for the n_env envs (env.get_graph's argument);
+        when given, every run starts from that scene instead of a reset (the key then only seeds the policy
+        noise).  The fp32 device tensors are read in place on every run, so editing them between runs -- also
+        between replays of a captured engine -- runs the new scene."""
         self.env = env
         self.B = int(n_env)
         self.T = int(T or env.max_episode_steps)
@@ -51,7 +55,12 @@ class RolloutEngine:
         B, T, n, dev = self.B, self.T, env.num_agents, self.device
         self.buf = env.empty_graph((T + 1, B), dev)
         nf = env._obstacle_fields()
-        self.obstacles = (torch.empty((B, env._obstacle_rows(), nf), dtype=torch.float32, device=dev) if nf else None)
+        self.init_state = None
+        if init_state is not None:  # the steps read the scene's own Lidar records
+            self.init_state, self.obstacles = self._check_init_state(init_state)
+        else:
+            self.obstacles = (torch.empty((B, env._obstacle_rows(), nf), dtype=torch.float32, device=dev) if nf
+                              else None)
         self.actions = torch.zeros((T, B, n, env.action_dim), dtype=torch.float32, device=dev)
         self.rewards = torch.empty((T, B), dtype=torch.float32, device=dev)
         self.costs = torch.empty((T, B, n, env.n_cost), dtype=torch.float32, device=dev)
@@ -73,6 +82,24 @@ class RolloutEngine:
             self._streams = [torch.cuda.Stream(dev) for _ in range(self.lanes)]
             if self.mode == self.MODE_SAMPLE:
                 self.noise_all = torch.empty((T, B * n, env.action_dim), dtype=torch.float32, device=dev)
+
+    def _check_init_state(self, state):
+        """The scene as the kernels will read it on every run: env.get_graph's shapes for n_env envs, fp32 tensors
+        on the engine's device with contiguous rows (anything else would be copied, and a captured engine would
+        replay the copy).  Returns (state, the Lidar obstacle records or None)."""
+        agent, goal, third, B = self.env.state_rows(state, "init_state")
+        names = ("agent", "goal", self.env._third_name())
+        for name, t in zip(names, (agent, goal, third)):
+            if t is None:
+                continue
+            if t.shape[0] != self.B:
+                raise ValueError(f"init_state.{name} must hold {self.B} envs, got {tuple(t.shape)}")
+            if t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"init_state.{name} must be a float32 tensor on {self.device}, got {t.dtype} on "
+                                 f"{t.device}")
+            if t.stride(-1) != 1 or t.stride(-2) != t.shape[-1]:
+                raise ValueError(f"init_state.{name} must have contiguous rows, got strides {tuple(t.stride())}")
+        return tuple(state), (third if self.env._obstacle_fields() > 0 else None)
 
     def graph_at(self, t: int) -> GraphsTuple:
         b = self.buf
@@ -110,6 +137,18 @@ class RolloutEngine:
 
     def _run(self):
         env = self.env
+        if self.init_state is not None:  # graph 0 of the caller's scene in place of the reset
+            cur = env.get_graph(self.init_state, out=self.graph_at(0))
+            if self.mode == self.MODE_RANDOM and self.lanes == 1 and self.fused:
+                env.rollout_into(self.buf, self.obstacles, self.actions, self.rewards, self.costs)
+            elif self.lanes > 1:
+                self._run_lanes()
+            else:
+                for t in range(self.T):
+                    if self.mode != self.MODE_RANDOM:
+                        self._act(t)
+                    cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
+            return
         if self.mode == self.MODE_RANDOM and self.lanes == 1 and self.fused:
             # env-only rollout: the states-only reset + ONE persistent launch for all T steps (graph 0 built
             # by the rollout kernel; configs without it loop the step kernel inside the call)

@@ -187,6 +187,36 @@ int dgppo_env_reset(const dgppo_env_cfg* cfg, const dgppo_env_reset_io* io, void
  * without a persistent rollout kernel get the full reset (the graph is written too). */
 int dgppo_env_reset_states(const dgppo_env_cfg* cfg, const dgppo_env_reset_io* io, void* stream);
 
+/* The graph of caller-given states: replaces `vmap(env.get_graph)` (with get_lidar_data) —
+ *   LidarEnv.get_lidar_data / get_graph dgppo/env/lidar_env/base.py:126-140, 227-271, MPE.get_graph
+ *   dgppo/env/mpe/base.py:211-241, the abstract door dgppo/env/base.py:137.
+ * Inputs, each with its own per-env stride (elements): `agent` (n, sd) rows; `goal` (n_goal_rows, sd) rows
+ * (cfg n_goals: 2 for the line variants, 1 for formation, else n); `third` = the Lidar obstacle records (O, 16)
+ * or the MPE obstacle states (O, 4), NULL allowed when n_obs == 0; `ray_dirs` as for dgppo_env_step.  Outputs
+ * as dgppo_env_reset writes them.  Nothing is clipped (the reference's get_graph does not clip), so states
+ * outside state_lim and obstacles outside the arena are legal; inputs must be finite.  One launch on `stream`, no
+ * host synchronisation, no allocation.  An env's outputs may alias that env's own inputs (rows are staged before
+ * any store).  The VMAS engines return DGPPO_EINVAL (their record carries contact-physics state). */
+typedef struct dgppo_env_graph_io {
+  const float* agent;       int64_t agent_stride;
+  const float* goal;        int64_t goal_stride;
+  const float* third;       int64_t third_stride;
+  const float* ray_dirs;
+  float* nodes;             int64_t nodes_stride;
+  float* edges;             int64_t edges_stride;
+  float* out_states;        int64_t out_states_stride;
+  int32_t* receivers;       int32_t* senders; int64_t edge_index_stride;
+  int32_t n_env;
+} dgppo_env_graph_io;
+
+int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_graph_io* io, void* stream);
+
+/* Host-side helper: `count` obstacle records (count x 16, DGPPO_OBST_FIELDS layout) from HOST arrays center
+ * (count x 2), width, height, theta (count each) = Rectangle.create (dgppo/env/obstacle.py:39-56) with the fp32
+ * sin / cos and operation order of the reset kernels, so a scene can be assembled without a GPU. */
+int dgppo_make_rectangles(int64_t count, const float* center, const float* width, const float* height,
+                          const float* theta, float* out);
+
 /* T env steps with given actions in one call: replaces the env half of the reference's rollout scan
  * `lax.scan(body, ...)` over env.step (dgppo/trainer/utils.py:45-55) for a fixed action sequence.
  * `step` describes graph 0 and step 0: graph t's rows live at the graph pointers + t * t_<field>

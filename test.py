@@ -7,7 +7,12 @@ test.py:100-139), optionally on a different agent / obstacle count or env than t
 Episodes are environments: episode i is env i of ONE batched rollout (Philox keyed (--seed, i)),
 so `--epi 1000` is a single hipGraph replay over 1000 envs; `--offset k` skips the first k
 episodes, as the reference's `test_keys[offset:]` does.  Rendering is out of scope,
-so --no-video / --dpi are accepted and ignored; --cpu / --debug too (there is no CPU path)."""
+so --no-video / --dpi are accepted and ignored; --cpu / --debug too (there is no CPU path).
+
+Beyond the reference: `--scene PATH` evaluates on the initial states stored in a scene file
+(dgppo_fov_amd/utils/scene.py) instead of seeds -- episodes are rows [offset:epi] of the file, all of its rows when
+--epi is not given -- and `--dump-scene PATH` writes the initial states of the episodes that ran, so
+`--dump-scene s.npz` then `--scene s.npz` replays the same episodes (deterministic policy: the same numbers)."""
 import argparse
 import os
 
@@ -50,13 +55,33 @@ def test(args):
     print("step: ", step)
     algo.load(model_path, step)  # the networks are agent-count agnostic: -n may differ from training
 
+    scene = None
+    if args.scene is not None:
+        from dgppo_fov_amd.utils.scene import load_scene
+
+        scene = load_scene(args.scene, env, dev)
+        rows = int(scene[0].shape[0])
+        if args.epi is None:
+            args.epi = rows
+        if rows < args.epi:
+            raise SystemExit(f"--scene {args.scene} holds {rows} episodes, fewer than --epi {args.epi}")
+    elif args.epi is None:
+        args.epi = 5
     episodes = list(range(args.offset, args.epi))
     if not episodes:
         raise SystemExit(f"--offset {args.offset} leaves no episodes of --epi {args.epi}")
     mode = RolloutEngine.MODE_SAMPLE if args.stochastic else RolloutEngine.MODE_DET
+    init_state = None
+    if scene is not None:  # episodes are rows [offset:epi] of the file
+        cut = lambda t: None if t is None else t[args.offset:args.epi]  # noqa: E731
+        init_state = type(scene)(*(cut(part) for part in scene))
     eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
-                        mode=mode)
+                        mode=mode, init_state=init_state)
     roll = eng.run(args.seed)
+    if args.dump_scene is not None:
+        from dgppo_fov_amd.utils.scene import save_scene
+
+        save_scene(args.dump_scene, env, eng.graph_at(0).env_states)
     rewards = roll.rewards.sum(1).double().cpu().numpy()  # (epi,)
     costs = roll.costs.amax(dim=(1, 2, 3)).double().cpu().numpy()
     # unsafe_mask on the pre-step graphs: the stored costs ARE env.get_cost(rollout.graph)
@@ -79,7 +104,9 @@ def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--path", type=str, required=True)
     parser.add_argument("--no-video", action="store_true", default=False)
-    parser.add_argument("--epi", type=int, default=5)
+    parser.add_argument("--epi", type=int, default=None)  # 5 without --scene, every row of the file with it
+    parser.add_argument("--scene", type=str, default=None)
+    parser.add_argument("--dump-scene", type=str, default=None)
     parser.add_argument("--step", type=int, default=None)
     parser.add_argument("--obs", type=int, default=None)
     parser.add_argument("--stochastic", action="store_true", default=False)
@@ -93,7 +120,7 @@ def main():
     parser.add_argument("--env", type=str, default=None)
     parser.add_argument("--offset", type=int, default=0)
     parser.add_argument("--dpi", type=int, default=100)
-    test(parser.parse_args())
+    return test(parser.parse_args())
 
 
 if __name__ == "__main__":
