@@ -139,6 +139,21 @@ class EnvGraphIO(ctypes.Structure):  # dgppo_env_graph_io
     ]
 
 
+RENDER_FOV = 1  # include/dgppo_hip.h DGPPO_RENDER_FOV
+
+
+class RenderArgs(ctypes.Structure):  # dgppo_render_args
+    _fields_ = [
+        ("states", c_f32p), ("states_estride", ctypes.c_int64), ("states_tstride", ctypes.c_int64),
+        ("receivers", c_f32p), ("senders", c_f32p), ("index_estride", ctypes.c_int64),
+        ("index_tstride", ctypes.c_int64),
+        ("obstacles", c_f32p), ("obstacles_estride", ctypes.c_int64),
+        ("out", c_f32p),
+        ("n_frames", ctypes.c_int32), ("frames_per_episode", ctypes.c_int32), ("size", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+    ]
+
+
 class EnvRolloutIO(ctypes.Structure):
     _fields_ = [
         ("step", EnvStepIO),
@@ -305,6 +320,7 @@ SIGNATURES = {
     "dgppo_env_rollout": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvRolloutIO), ctypes.c_void_p]),
     "dgppo_env_get_graph": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphIO), ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
+    "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_gemm_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs)]),
     "dgppo_gemm_wgrad_grouped_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs), ctypes.c_int]),
     "dgppo_gemm_wgrad_grouped": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_int, c_f32p, ctypes.c_void_p]),
@@ -381,7 +397,10 @@ def load() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # a library built before the symbol was added (the ABI number covers struct layouts only)
+            raise NativeLibraryError(f"{LIB_PATH} lacks the symbol {name}: rebuild (`make`)") from None
         fn.restype = res
         fn.argtypes = args
     if lib.dgppo_abi_version() != ABI_VERSION:  # the ctypes mirrors below describe ABI_VERSION's structs

@@ -1,0 +1,298 @@
+// Rollout frames rasterised on the GPU (dgppo_render_frames): the drawing half of the reference's render_video
+// (dgppo/env/plot.py render_lidar / render_mpe) as ONE launch over (frame, pixel tile).
+//
+// Pixel rule (DESIGN.md "Rendering"): the world square [0, L]^2 maps onto S x S pixels of pitch h = L / S, pixel
+// (row, col) samples p = ((col + 0.5) h, (S - row - 0.5) h); every shape has a signed distance d(p), its coverage is
+// clamp(0.5 - d / h, 0, 1), and the shapes are composited in painter's order in fp32 on straight sRGB values,
+// c += alpha * cov * (col - c) from white; the stored byte is floor(255 c + 0.5), A = 255.
+//
+// A 256-thread workgroup owns one 32 x 32 pixel tile of one frame (4 pixels per thread; a wave stores two rows of 32
+// adjacent pixels, 128 contiguous bytes each).  The frame's primitives -- MPE obstacle circles, FoV wedges, edges, goal
+// and agent circles, Lidar rectangles, in that order -- are numbered 0 .. P-1 and processed in chunks of 256: thread i
+// builds primitive chunk * 256 + i from the state rows, drops it when it is invalid (pad / out-of-range edge index,
+// non-finite coordinate), when its bounding box, grown by one pixel pitch, misses the tile's pixel centres, or when its
+// signed distance at the tile's centre exceeds the tile's half-diagonal by more than one pixel pitch, and a ballot /
+// prefix rank compacts the survivors IN ORDER into an LDS list; after a barrier every pixel walks the list (all lanes
+// read the same entry: LDS broadcasts).  A dropped primitive has d >= h on every pixel centre of the tile (d is bounded
+// below by the distance to its bounding circle / box, and the four signed distances are exact, hence 1-Lipschitz),
+// i.e. coverage exactly 0, so culling never changes a byte.  No atomics, no data-dependent ordering: two launches give
+// identical bytes.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/dgppo_hip.h"
+#include "vmas.h"
+
+namespace dgppo {
+namespace {
+
+constexpr int kThreads = 256, kTileW = 32, kTileH = 32, kPix = kTileW * kTileH / kThreads;  // 4 rows per thread
+constexpr int kRowStep = kThreads / kTileW;  // rows between a thread's pixels
+constexpr int kCircle = 0, kRect = 1, kEdge = 2, kWedge = 3;
+// colours: 0 obstacle #8a0000, 1 agent / wedge #0068ff, 2 goal / goal edge #2fdd00, 3 edge #333333
+constexpr int kRed = 0, kBlue = 1, kGreen = 2, kGrey = 3;
+
+struct Prim {        // 32 B
+  float a[6];        // circle: cx cy r | rect: cx cy w/2 h/2 cos sin | edge: ax ay bx by | wedge: cx cy hx hy (unit)
+  int32_t kind;      // shape | colour << 8
+  float alpha;
+};
+
+struct Params {
+  const float* states;
+  const int32_t* receivers;
+  const int32_t* senders;
+  const float* obstacles;
+  uint32_t* out;
+  int64_t s_es, s_ts, i_es, i_ts, o_es;
+  int32_t fpe, S, tiles_x, tiles_per_frame;
+  int32_t n, ng, O, N, E, sd;
+  int32_t nA, nB, nC, nD, nE;  // primitives per layer: MPE circles, wedges, edges, goal + agent circles, rectangles
+  float L, h, inv_h, car_r, obs_r, fov_r, sin_b, cos_b, edge_hw;
+};
+
+__device__ __forceinline__ bool fin(float x) { return fabsf(x) <= 3.4028234664e38f; }  // false for NaN / inf
+
+// Primitive k of the frame, or kind < 0 when it contributes nothing.  bb = its bounding box [x0, x1, y0, y1].
+__device__ __forceinline__ Prim build(const Params& P, const float* __restrict__ st, const int32_t* __restrict__ rc,
+                                      const int32_t* __restrict__ sn, const float* __restrict__ ob, int k, float bb[4]) {
+  Prim q;
+  q.kind = -1;
+  q.alpha = 1.0f;
+  for (int i = 0; i < 6; ++i) q.a[i] = 0.0f;
+  float cx = 0.0f, cy = 0.0f, R = 0.0f;  // bounding circle (edges set bb themselves)
+  bool have_bb = false;
+  if (k < P.nA) {  // MPE obstacle circle, state row n + ng + k
+    const float* s = st + (int64_t)(P.n + P.ng + k) * P.sd;
+    cx = s[0], cy = s[1], R = P.obs_r;
+    if (fin(cx) && fin(cy)) q.kind = kCircle | (kRed << 8);
+    q.a[0] = cx, q.a[1] = cy, q.a[2] = R;
+  } else if ((k -= P.nA) < P.nB) {  // FoV wedge of agent k
+    const float* s = st + (int64_t)k * P.sd;
+    cx = s[0], cy = s[1], R = P.fov_r;
+    const float hx = s[2], hy = s[3];
+    if (fin(cx) && fin(cy) && fin(hx) && fin(hy)) q.kind = kWedge | (kBlue << 8);
+    const float inv = 1.0f / fmaxf(sqrtf(hx * hx + hy * hy), 1e-12f);
+    q.a[0] = cx, q.a[1] = cy, q.a[2] = hx * inv, q.a[3] = hy * inv;
+    q.alpha = 0.15f;
+  } else if ((k -= P.nB) < P.nC) {  // edge k: capsule sender -> receiver
+    const int r = rc[k], s = sn[k];
+    if (r >= 0 && s >= 0 && r < P.N - 1 && s < P.N - 1) {  // N - 1 is the pad node
+      const float* a = st + (int64_t)s * P.sd;
+      const float* b = st + (int64_t)r * P.sd;
+      const float ax = a[0], ay = a[1], bx = b[0], by = b[1];
+      if (fin(ax) && fin(ay) && fin(bx) && fin(by))
+        q.kind = kEdge | ((s >= P.n && s < P.n + P.ng ? kGreen : kGrey) << 8);
+      q.a[0] = ax, q.a[1] = ay, q.a[2] = bx, q.a[3] = by;
+      const float m = P.edge_hw + P.h;
+      bb[0] = fminf(ax, bx) - m, bb[1] = fmaxf(ax, bx) + m, bb[2] = fminf(ay, by) - m, bb[3] = fmaxf(ay, by) + m;
+      have_bb = true;
+    }
+    q.alpha = 0.5f;
+  } else if ((k -= P.nC) < P.nD) {  // goal circles ng-1 .. 0, then agent circles n-1 .. 0
+    const bool goal = k < P.ng;
+    const int row = goal ? P.n + (P.ng - 1 - k) : P.n - 1 - (k - P.ng);
+    const float* s = st + (int64_t)row * P.sd;
+    cx = s[0], cy = s[1], R = P.car_r;
+    if (fin(cx) && fin(cy)) q.kind = kCircle | ((goal ? kGreen : kBlue) << 8);
+    q.a[0] = cx, q.a[1] = cy, q.a[2] = R;
+  } else if ((k -= P.nD) < P.nE) {  // Lidar obstacle rectangle k
+    const float* o = ob + (int64_t)k * DGPPO_OBST_FIELDS;
+    cx = o[0], cy = o[1];
+    const float hw = 0.5f * o[2], hh = 0.5f * o[3], c = o[5], s = o[6];
+    if (fin(cx) && fin(cy) && fin(hw) && fin(hh) && fin(c) && fin(s)) q.kind = kRect | (kRed << 8);
+    q.a[0] = cx, q.a[1] = cy, q.a[2] = hw, q.a[3] = hh, q.a[4] = c, q.a[5] = s;
+    R = sqrtf(hw * hw + hh * hh);
+    // the bounds on d hold only for a rotation; records with another (cos, sin) are never culled
+    if (!(fabsf(c * c + s * s - 1.0f) <= 1e-3f)) R = INFINITY, q.alpha = -1.0f;
+  }
+  if (!have_bb) {
+    const float m = R + P.h;
+    bb[0] = cx - m, bb[1] = cx + m, bb[2] = cy - m, bb[3] = cy + m;
+  }
+  return q;
+}
+
+__device__ __forceinline__ float sgn(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+
+__device__ __forceinline__ float distance(const Prim& q, int shape, float px, float py, const Params& P) {
+  if (shape == kCircle) {
+    const float dx = px - q.a[0], dy = py - q.a[1];
+    return sqrtf(dx * dx + dy * dy) - q.a[2];
+  }
+  if (shape == kEdge) {
+    const float pax = px - q.a[0], pay = py - q.a[1], bax = q.a[2] - q.a[0], bay = q.a[3] - q.a[1];
+    const float t = fminf(fmaxf((pax * bax + pay * bay) / fmaxf(bax * bax + bay * bay, 1e-12f), 0.0f), 1.0f);
+    const float ex = pax - t * bax, ey = pay - t * bay;
+    return sqrtf(ex * ex + ey * ey) - P.edge_hw;
+  }
+  if (shape == kRect) {
+    const float dx = px - q.a[0], dy = py - q.a[1], c = q.a[4], s = q.a[5];
+    const float qx = fabsf(c * dx + s * dy) - q.a[2], qy = fabsf(c * dy - s * dx) - q.a[3];
+    const float ox = fmaxf(qx, 0.0f), oy = fmaxf(qy, 0.0f);
+    return sqrtf(ox * ox + oy * oy) + fminf(fmaxf(qx, qy), 0.0f);
+  }
+  // wedge: exact circular-sector distance in the heading frame, (v, u) = (across, along)
+  const float dx = px - q.a[0], dy = py - q.a[1], hx = q.a[2], hy = q.a[3];
+  const float u = dx * hx + dy * hy, v = fabsf(dx * hy - dy * hx);
+  const float l = sqrtf(u * u + v * v) - P.fov_r;
+  const float kk = fminf(fmaxf(v * P.sin_b + u * P.cos_b, 0.0f), P.fov_r);
+  const float mv = v - kk * P.sin_b, mu = u - kk * P.cos_b;
+  const float m = sqrtf(mv * mv + mu * mu);
+  return fmaxf(l, m * sgn(P.cos_b * v - P.sin_b * u));
+}
+
+__global__ __launch_bounds__(kThreads) void render_kernel(const Params P) {
+  __shared__ Prim list[kThreads];
+  __shared__ int wave_count[kThreads / 64];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int frame = blockIdx.x / P.tiles_per_frame, tile = blockIdx.x % P.tiles_per_frame;
+  const int ty = tile / P.tiles_x, tx = tile % P.tiles_x;
+  const int e = frame / P.fpe, t = frame % P.fpe;
+  const float* st = P.states + e * P.s_es + t * P.s_ts;
+  const int32_t* rc = P.receivers + e * P.i_es + t * P.i_ts;
+  const int32_t* sn = P.senders + e * P.i_es + t * P.i_ts;
+  const float* ob = P.obstacles + e * P.o_es;
+
+  // this thread's pixels: column col, rows row0 + kRowStep j
+  const int col = tx * kTileW + (tid & (kTileW - 1)), row0 = ty * kTileH + tid / kTileW;
+  const float px = ((float)col + 0.5f) * P.h;
+  float py[kPix], cr[kPix], cg[kPix], cb[kPix];
+#pragma unroll
+  for (int j = 0; j < kPix; ++j) {
+    py[j] = ((float)(P.S - (row0 + kRowStep * j)) - 0.5f) * P.h;
+    cr[j] = cg[j] = cb[j] = 1.0f;
+  }
+  // the tile's pixel centres span [x0, x1] x [y0, y1]
+  const int c1 = min(tx * kTileW + kTileW, P.S), r1 = min(ty * kTileH + kTileH, P.S);
+  const float x0 = ((float)(tx * kTileW) + 0.5f) * P.h, x1 = ((float)c1 - 0.5f) * P.h;
+  const float y1 = ((float)(P.S - ty * kTileH) - 0.5f) * P.h, y0 = ((float)(P.S - r1) + 0.5f) * P.h;
+  const float mx = 0.5f * (x0 + x1), my = 0.5f * (y0 + y1);
+  const float reach = 0.5f * sqrtf((x1 - x0) * (x1 - x0) + (y1 - y0) * (y1 - y0)) + P.h;  // half-diagonal + one pitch
+
+  const int total = P.nA + P.nB + P.nC + P.nD + P.nE;
+  for (int base = 0; base < total; base += kThreads) {
+    const int k = base + tid;
+    float bb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    Prim q;
+    q.kind = -1;
+    if (k < total) q = build(P, st, rc, sn, ob, k, bb);
+    // finiteness was tested in build(); the box test is on floats, nothing is converted to an integer
+    bool keep = q.kind >= 0 && !(bb[1] < x0 || bb[0] > x1 || bb[3] < y0 || bb[2] > y1);
+    if (keep && q.alpha >= 0.0f) keep = !(distance(q, q.kind & 0xff, mx, my, P) > reach);  // NaN keeps
+    q.alpha = fabsf(q.alpha);
+    const unsigned long long mask = __ballot(keep);
+    const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_count[wave] = __popcll(mask);
+    __syncthreads();
+    int offset = 0, count = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+      const int c = wave_count[w];
+      offset += w < wave ? c : 0;
+      count += c;
+    }
+    if (keep) list[offset + rank] = q;
+    __syncthreads();
+    for (int i = 0; i < count; ++i) {
+      const Prim s = list[i];
+      const int shape = s.kind & 0xff, colour = s.kind >> 8;
+      // #8a0000, #0068ff, #2fdd00, #333333
+      const float r = colour == kRed ? 138 / 255.0f : colour == kBlue ? 0.0f : colour == kGreen ? 47 / 255.0f : 51 / 255.0f;
+      const float g = colour == kRed ? 0.0f : colour == kBlue ? 104 / 255.0f : colour == kGreen ? 221 / 255.0f : 51 / 255.0f;
+      const float b = colour == kRed ? 0.0f : colour == kBlue ? 1.0f : colour == kGreen ? 0.0f : 51 / 255.0f;
+#pragma unroll
+      for (int j = 0; j < kPix; ++j) {
+        const float d = distance(s, shape, px, py[j], P);
+        const float w = s.alpha * fminf(fmaxf(0.5f - d * P.inv_h, 0.0f), 1.0f);
+        cr[j] += w * (r - cr[j]);
+        cg[j] += w * (g - cg[j]);
+        cb[j] += w * (b - cb[j]);
+      }
+    }
+    __syncthreads();  // the list and the counts are rewritten by the next chunk
+  }
+
+  if (col < P.S) {
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {
+      const int row = row0 + kRowStep * j;
+      if (row < P.S) {
+        const uint32_t R = (uint32_t)floorf(255.0f * cr[j] + 0.5f), G = (uint32_t)floorf(255.0f * cg[j] + 0.5f),
+                       B = (uint32_t)floorf(255.0f * cb[j] + 0.5f);
+        P.out[((int64_t)frame * P.S + row) * P.S + col] = R | (G << 8) | (B << 16) | 0xff000000u;
+      }
+    }
+  }
+}
+
+// [lo, hi) byte span of `count` frames of `elems` elements of 4 bytes under the two-level stride
+void span(const void* p, int64_t elems, int64_t episodes, int64_t es, int64_t fpe, int64_t ts, uintptr_t* lo,
+          uintptr_t* hi) {
+  *lo = (uintptr_t)p;
+  *hi = (uintptr_t)p + 4 * (uintptr_t)((episodes - 1) * es + (fpe - 1) * ts + elems);
+}
+
+}  // namespace
+}  // namespace dgppo
+
+extern "C" int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_args* a, void* stream) {
+  using namespace dgppo;
+  if (!cfg || !a) return DGPPO_EINVAL;
+  if (vmas::is_vmas(cfg)) return DGPPO_EINVAL;  // the VMAS reference renderers are separate code
+  if (cfg->engine < DGPPO_ENGINE_LIDAR || cfg->engine > DGPPO_ENGINE_OMNI) return DGPPO_EINVAL;
+  const bool mpe = cfg->engine == DGPPO_ENGINE_MPE, omni = cfg->engine == DGPPO_ENGINE_OMNI;
+  const int n = cfg->n_agents, O = cfg->n_obs, N = cfg->n_nodes, E = cfg->n_edges, sd = cfg->state_dim;
+  const int ng = cfg->n_goals > 0 ? cfg->n_goals : n;
+  if (n < 1 || O < 0 || E < 0 || sd < (omni ? 4 : 2) || N < n + ng + 1 || (mpe && N < n + ng + O + 1))
+    return DGPPO_EINVAL;
+  if (!(cfg->area_size > 0.0f) || !isfinite(cfg->area_size)) return DGPPO_EINVAL;
+  if (a->size < 1 || a->size > 32768 || a->n_frames < 0 || a->frames_per_episode < 1) return DGPPO_EINVAL;
+  if (a->n_frames == 0) return 0;
+  const bool rects = !mpe && O > 0;
+  if (!a->states || !a->out || (E > 0 && (!a->receivers || !a->senders)) || (rects && !a->obstacles))
+    return DGPPO_EINVAL;
+  if (a->states_estride < 0 || a->states_tstride < 0 || a->index_estride < 0 || a->index_tstride < 0 ||
+      a->obstacles_estride < 0)
+    return DGPPO_EINVAL;
+  const int64_t S = a->size, F = a->n_frames, fpe = a->frames_per_episode;
+  const int64_t episodes = (F + fpe - 1) / fpe, fl = F < fpe ? F : fpe;
+  const int64_t tiles_x = (S + kTileW - 1) / kTileW, tiles_y = (S + kTileH - 1) / kTileH;
+  if (F * tiles_x * tiles_y > 0x7fffffffLL) return DGPPO_EINVAL;
+  {  // `out` must not overlap the bytes an input spans
+    const uintptr_t o0 = (uintptr_t)a->out, o1 = o0 + (uintptr_t)(F * S * S * 4);
+    uintptr_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+    span(a->states, (int64_t)N * sd, episodes, a->states_estride, fl, a->states_tstride, &lo[0], &hi[0]);
+    if (E > 0) {
+      span(a->receivers, E, episodes, a->index_estride, fl, a->index_tstride, &lo[1], &hi[1]);
+      span(a->senders, E, episodes, a->index_estride, fl, a->index_tstride, &lo[2], &hi[2]);
+    }
+    if (rects) span(a->obstacles, (int64_t)O * DGPPO_OBST_FIELDS, episodes, a->obstacles_estride, 1, 0, &lo[3], &hi[3]);
+    for (int i = 0; i < 4; ++i)
+      if (lo[i] < o1 && o0 < hi[i]) return DGPPO_EINVAL;
+  }
+  Params P{};
+  P.states = a->states, P.receivers = a->receivers, P.senders = a->senders, P.obstacles = a->obstacles;
+  P.out = (uint32_t*)a->out;
+  P.s_es = a->states_estride, P.s_ts = a->states_tstride, P.i_es = a->index_estride, P.i_ts = a->index_tstride;
+  P.o_es = a->obstacles_estride;
+  P.fpe = (int32_t)fpe, P.S = (int32_t)S, P.tiles_x = (int32_t)tiles_x, P.tiles_per_frame = (int32_t)(tiles_x * tiles_y);
+  P.n = n, P.ng = ng, P.O = O, P.N = N, P.E = E, P.sd = sd;
+  P.nA = mpe ? O : 0;
+  P.nB = omni && (a->flags & DGPPO_RENDER_FOV) ? n - 1 : 0;
+  P.nC = E;
+  P.nD = ng + n;
+  P.nE = rects ? O : 0;
+  P.L = cfg->area_size;
+  P.h = cfg->area_size / (float)S;
+  P.inv_h = 1.0f / P.h;
+  P.car_r = cfg->car_radius, P.obs_r = cfg->obs_radius, P.fov_r = cfg->fov_rmax;
+  const double beta = (double)cfg->fov_angle_deg * (3.14159265358979323846 / 180.0);
+  P.sin_b = (float)sin(beta), P.cos_b = (float)cos(beta);
+  P.edge_hw = cfg->area_size / 720.0f;  // the reference's 2 pt line on its 10 in figure
+  hipLaunchKernelGGL(render_kernel, dim3((unsigned)(F * tiles_x * tiles_y)), dim3(kThreads), 0, (hipStream_t)stream, P);
+  return (int)hipGetLastError();
+}

@@ -448,6 +448,115 @@ class MultiAgentEnv(ABC):
         done = torch.zeros(B, dtype=torch.bool, device=graph.states.device)
         return StepResult(g, reward, cost, done, {})
 
+    # ---- rendering -----------------------------------------------------------------------------------
+    _VMAS_ENGINES = (_lib.DGPPO_ENGINE_VMAS_WHEEL, _lib.DGPPO_ENGINE_VMAS_TRANSPORT)
+
+    def render_frames(self, graph: GraphsTuple, size: Optional[int] = None, dpi: int = 100,
+                      viz_opts: Optional[dict] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The scene of every graph of `graph` (batch shape (B,) or (B, T), e.g. the strided `rollout.graph` view) as a
+        uint8 RGBA image (*batch, S, S, 4) on the graph's device, S = size or 10 * dpi (the reference's 10 in figure):
+        one HIP launch over (frame, pixel tile) (torch.ops.dgppo.render_frames; DESIGN.md "Rendering" has the pixel
+        rule and the layers).  viz_opts={"fov": False} leaves out the FoV wedges LidarOmniTarget draws by default.
+        `out` reuses a contiguous uint8 buffer of that shape.  There is no host path: a CPU graph raises."""
+        if self.ENGINE in self._VMAS_ENGINES:
+            raise NotImplementedError(f"{type(self).__name__}: rendering the VMAS envs is not built (their reference "
+                                      "renderers are separate code)")
+        viz_opts = viz_opts or {}
+        for key in ("cbf", "Vh"):
+            if key in viz_opts:
+                raise NotImplementedError(f"viz_opts[{key!r}] (the reference's contour overlay): not built")
+        _lib.require_gpu(graph.states.device, "env.render_frames")
+        states, recv, send = graph.states, graph.receivers, graph.senders
+        bs = tuple(states.shape[:-2])
+        if len(bs) not in (1, 2) or tuple(states.shape[-2:]) != (self.n_nodes, self.state_dim):
+            raise ValueError("render_frames: graph must have batch shape (B,) or (B, T) and this env's layout")
+        S = int(size) if size else 10 * int(dpi)
+        if S < 1:
+            raise ValueError(f"render_frames: image size must be >= 1, got {S}")
+        ob = self._obstacles_of(graph) if self._obstacle_fields() > 0 else None
+        if ob is not None and len(bs) == 2:  # one obstacle set per episode: the (B, T) views expand it over T
+            if ob.shape[1] > 1 and ob.stride(1) != 0:
+                raise ValueError("render_frames: a (B, T) graph needs one obstacle set per episode")
+            ob = ob[:, 0]
+        shape = bs + (S, S, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=states.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != states.device:
+            raise ValueError(f"render_frames: out must be a uint8 {shape} tensor on {states.device}")
+        flags = _lib.RENDER_FOV if viz_opts.get("fov", True) else 0
+        torch.ops.dgppo.render_frames(self._cfg_handle, states, recv, send, ob, out, flags)
+        return out
+
+    def render_video(self, rollout, video_path, Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
+                     episode: int = 0, max_frame_bytes: int = 1 << 30) -> str:
+        """The reference's render_video (dgppo/env/base.py:141, plot.py render_lidar / render_mpe) for episode
+        `episode` of a batched Rollout: the T frames of rollout.graph[episode] are rasterised on the GPU
+        (render_frames, in chunks whose device buffer stays within max_frame_bytes) and copied to the host, where
+        Pillow draws the header band above the scene (per-component max cost, reward, unsafe agents, kk) and the
+        agent indices and encodes an animated GIF at 30 fps.  A `.mp4` suffix is rewritten to `.gif` (no ffmpeg);
+        the path written is returned.  Ta_is_unsafe: (T, n) booleans (test.py: any(cost >= 0))."""
+        import pathlib
+
+        try:
+            from PIL import Image, ImageDraw, ImageFont
+        except ImportError as e:
+            raise ImportError("render_video needs Pillow for the text and the GIF; env.render_frames returns the "
+                              "frames without it") from e
+        if self.ENGINE in self._VMAS_ENGINES:
+            raise NotImplementedError(f"{type(self).__name__}: rendering the VMAS envs is not built (their reference "
+                                      "renderers are separate code)")
+        g = rollout.graph
+        if g.states.dim() != 4 or g.states.shape[1] < 1:
+            raise ValueError("render_video: rollout.graph must have batch shape (B, T) with T >= 1")
+        T, n, S = int(g.states.shape[1]), self._num_agents, 10 * int(dpi)
+        band = S // 8
+        per = max(1, int(max_frame_bytes) // (S * S * 4))
+        ob = self._obstacles_of(g) if self._obstacle_fields() > 0 and self.ENGINE not in self._VMAS_ENGINES else None
+        costs = rollout.costs[episode].amax(dim=1).double().cpu().numpy()  # (T, n_cost) max over agents
+        rewards = rollout.rewards[episode].double().cpu().numpy()
+        pos = g.states[episode, :, :n, :2].double().cpu().numpy()  # (T, n, 2)
+        unsafe = None if Ta_is_unsafe is None else np.asarray(
+            Ta_is_unsafe.cpu() if isinstance(Ta_is_unsafe, torch.Tensor) else Ta_is_unsafe).astype(bool)
+        names = self.cost_components
+        lines = 2 + len(names)
+        px = max(6, band // (lines + 1))
+        frames, h = [], self._area_size / S
+        lpx = max(px, int(1.4 * float(self._params.get("car_radius", 0.05)) / h))  # labels: about the agent's radius
+        try:
+            font, label_font = ImageFont.load_default(size=px), ImageFont.load_default(size=lpx)
+        except (TypeError, OSError):  # a Pillow without the scalable default font
+            font = label_font = ImageFont.load_default()
+            lpx = px
+        for t0 in range(0, T, per):
+            t1 = min(T, t0 + per)
+            sub = self._assemble(g.nodes[episode, t0:t1], g.edges[episode, t0:t1], g.states[episode, t0:t1],
+                                 g.receivers[episode, t0:t1], g.senders[episode, t0:t1],
+                                 None if ob is None else ob[episode, t0:t1])
+            rgb = self.render_frames(sub, size=S, viz_opts=viz_opts)[..., :3].cpu().numpy()
+            for t in range(t0, t1):
+                im = Image.new("RGB", (S, S + band), "white")
+                im.paste(Image.fromarray(rgb[t - t0], "RGB"), (0, band))
+                d = ImageDraw.Draw(im)
+                text = "Cost:\n" + "\n".join(f"    {nm}: {costs[t, i]:5.4f}" for i, nm in enumerate(names))
+                d.multiline_text((S // 50, 0), text + f"\nReward: {rewards[t]:5.4f}", fill="black", font=font, spacing=0)
+                right = [f"kk={t:04}"]
+                if unsafe is not None and t < len(unsafe):
+                    right.append("Unsafe: [" + " ".join(str(i) for i in np.where(unsafe[t])[0]) + "]")  # one line
+                for i, s in enumerate(right):
+                    d.text((S - S // 100 - d.textlength(s, font=font), i * px), s, fill="black", font=font)
+                for i in range(n):
+                    x, y = pos[t, i]
+                    if np.isfinite(x) and np.isfinite(y) and 0 <= x <= self._area_size and 0 <= y <= self._area_size:
+                        d.text((x / h - d.textlength(str(i), font=label_font) / 2, band + S - y / h - 0.6 * lpx), str(i),
+                               fill="black", font=label_font)
+                frames.append(im.convert("P", palette=Image.Palette.ADAPTIVE, colors=64))
+        path = pathlib.Path(video_path)
+        if path.suffix.lower() != ".gif":
+            path = path.with_suffix(".gif")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        frames[0].save(path, save_all=True, append_images=frames[1:], duration=1000 // 30, loop=0, optimize=False)
+        return str(path)
+
     def get_cost(self, graph: GraphsTuple) -> torch.Tensor:
         """Cost of a graph (lidar_env/base.py:180-207): the step kernel evaluates it on its input."""
         zero = torch.zeros(graph.states.shape[:-2] + (self._num_agents, self.action_dim), device=graph.states.device)

@@ -12,6 +12,7 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::env_reset_states dgppo_env_reset_states  the sampling half of env_reset (no graph)
   dgppo::env_rollout    dgppo_env_rollout    lax.scan of env.step over T given actions, trainer/utils.py:45-55
   dgppo::env_get_graph  dgppo_env_get_graph  vmap(env.get_graph)  lidar_env/base.py:126-140, 227-271, mpe/base.py:211-241
+  dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
   dgppo::gnn_attn_bwd   dgppo_gnn_attn_bwd   its gradient (the jax.grad of update_Vl / update_policy)
   dgppo::gae            dgppo_gae            compute_dec_ocp_gae, algo/utils.py:11-79
@@ -233,6 +234,52 @@ def env_get_graph(cfg: int, agent: Tensor, goal: Tensor, third: Optional[Tensor]
 
 @env_get_graph.register_fake
 def _env_get_graph_fake(cfg, agent, goal, third, ray_dirs, nodes, edges, states, receivers, senders) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::render_frames", mutates_args=("out",))
+def render_frames(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, obstacles: Optional[Tensor],
+                  out: Tensor, flags: int) -> None:
+    """Rasterise the frames of a graph batch: states (B, N, sd) or (B, T, N, sd) with receivers / senders (B[, T], E)
+    int32 and the Lidar obstacle records (B, O, 16) (one set per episode; None for MPE or n_obs == 0) -> out, a
+    contiguous uint8 (B[, T], S, S, 4) RGBA image stack.  The batch strides are free (the (B, T) view of a time-major
+    rollout buffer passes without a copy); the trailing dims must be contiguous.  flags bit 0: FoV wedges."""
+    _lib.require_gpu(states.device, "dgppo::render_frames")
+    _lib.require_gpu(out.device, "dgppo::render_frames")
+    nb = states.dim() - 2
+    if nb not in (1, 2) or receivers.dim() != nb + 1 or receivers.shape != senders.shape or \
+            receivers.shape[:nb] != states.shape[:nb]:
+        raise ValueError("render_frames: states (B[, T], N, sd) with receivers / senders (B[, T], E)")
+    if states.dtype != torch.float32 or receivers.dtype != torch.int32 or senders.dtype != torch.int32:
+        raise ValueError("render_frames: float32 states and int32 receivers / senders")
+    frames = int(states.shape[0]) * (int(states.shape[1]) if nb == 2 else 1)
+    if out.dtype != torch.uint8 or out.dim() < 3 or not out.is_contiguous() or out.shape[-1] != 4 or \
+            out.shape[-2] != out.shape[-3] or out.numel() != frames * 4 * int(out.shape[-2]) ** 2:
+        raise ValueError("render_frames: out must be a contiguous uint8 (frames, S, S, 4) tensor")
+    if receivers.stride()[:nb] != senders.stride()[:nb]:
+        raise ValueError("render_frames: receivers and senders need the same batch strides")
+    a = _lib.RenderArgs()
+    for t, inner in ((states, 2), (receivers, 1), (senders, 1)):
+        _stride(t, inner)  # raises unless the trailing dims are contiguous
+    a.states, a.states_estride, a.states_tstride = _p(states), states.stride(0), (states.stride(1) if nb == 2 else 0)
+    a.receivers, a.senders = _p(receivers), _p(senders)
+    a.index_estride, a.index_tstride = receivers.stride(0), (receivers.stride(1) if nb == 2 else 0)
+    if obstacles is not None:
+        if obstacles.dim() != 3 or obstacles.shape[0] != states.shape[0] or obstacles.dtype != torch.float32:
+            raise ValueError("render_frames: obstacles must be float32 (B, O, 16), one set per episode")
+        _stride(obstacles, 2)
+        a.obstacles, a.obstacles_estride = _p(obstacles), obstacles.stride(0)
+    a.out = _p(out)
+    a.n_frames, a.frames_per_episode = frames, (int(states.shape[1]) if nb == 2 else 1)
+    a.size, a.flags = int(out.shape[-2]), int(flags)
+    if frames == 0:
+        return
+    _lib.check(_lib.load().dgppo_render_frames(ctypes.byref(env_cfg(cfg)), ctypes.byref(a), _stream(states)),
+               "dgppo_render_frames")
+
+
+@render_frames.register_fake
+def _render_frames_fake(cfg, states, receivers, senders, obstacles, out, flags) -> None:
     return None
 
 

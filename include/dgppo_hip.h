@@ -217,6 +217,30 @@ int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_graph_io* io, 
 int dgppo_make_rectangles(int64_t count, const float* center, const float* width, const float* height,
                           const float* theta, float* out);
 
+/* Rollout frames rasterised on the GPU: replaces the drawing half of the reference's render_video (dgppo/env/plot.py
+ * render_lidar / render_mpe: matplotlib circles, rectangles and a LineCollection per frame); text and video
+ * encoding stay with the caller.  Frame f = e * frames_per_episode + t reads its (N, sd) state rows at states +
+ * e * states_estride + t * states_tstride and its (E) edge indices at receivers / senders + e * index_estride +
+ * t * index_tstride (element strides: the (B, T) view of a time-major (T+1, B, ...) rollout buffer passes as it is;
+ * frames_per_episode = 1 with the frame stride in *_estride for a flat batch).  `obstacles`: the Lidar (O, 16)
+ * records of episode e at + e * obstacles_estride (NULL when n_obs == 0 and for the MPE engine, whose obstacles are
+ * state rows).  `out`: (n_frames, size, size, 4) uint8 RGBA, contiguous, A = 255, row 0 at the top.
+ * The pixel rule, the shapes' signed distances and the layer order are DESIGN.md's "Rendering" section.  Edge indices
+ * outside [0, N) and primitives with a non-finite coordinate are skipped, so caller-made graphs cannot cause an
+ * out-of-bounds read.  One launch on `stream`, no atomics: the same inputs give the same bytes.
+ * DGPPO_EINVAL: the VMAS engines, size < 1 (or > 32768), n_frames < 0, frames_per_episode < 1, a NULL required
+ * pointer, a negative stride, or `out` overlapping the bytes an input spans. */
+#define DGPPO_RENDER_FOV 1 /* flags bit 0: draw the FoV wedges (Omni engine) */
+typedef struct dgppo_render_args {
+  const float* states;        int64_t states_estride, states_tstride;
+  const int32_t* receivers;   const int32_t* senders; int64_t index_estride, index_tstride;
+  const float* obstacles;     int64_t obstacles_estride;
+  uint8_t* out;
+  int32_t n_frames, frames_per_episode, size, flags;
+} dgppo_render_args;
+
+int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_args* a, void* stream);
+
 /* T env steps with given actions in one call: replaces the env half of the reference's rollout scan
  * `lax.scan(body, ...)` over env.step (dgppo/trainer/utils.py:45-55) for a fixed action sequence.
  * `step` describes graph 0 and step 0: graph t's rows live at the graph pointers + t * t_<field>

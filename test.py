@@ -6,8 +6,15 @@ test.py:100-139), optionally on a different agent / obstacle count or env than t
 
 Episodes are environments: episode i is env i of ONE batched rollout (Philox keyed (--seed, i)),
 so `--epi 1000` is a single hipGraph replay over 1000 envs; `--offset k` skips the first k
-episodes, as the reference's `test_keys[offset:]` does.  Rendering is out of scope,
-so --no-video / --dpi are accepted and ignored; --cpu / --debug too (there is no CPU path).
+episodes, as the reference's `test_keys[offset:]` does.  --cpu / --debug are accepted and ignored (there is no CPU
+path).
+
+Videos are opt-in: `--video` renders the first `--max-videos` (default 5) evaluated episodes with env.render_video
+(frames rasterised on the GPU, header text and GIF encoding by Pillow on the host, --dpi honoured: the scene is
+10 * dpi pixels square) to `<path>/videos/<step>/<stamp>_n{n}_epi{ii:02}_reward..._cost..._sr....gif`, the reference's
+names with .gif for .mp4 (no ffmpeg).  The reference renders every episode unless --no-video is given; here the
+default is no video, so a 1000-episode evaluation does not encode 1000 GIFs, and --no-video stays accepted (it wins
+over --video).  The metric lines are the same with and without --video.
 
 Beyond the reference: `--scene PATH` evaluates on the initial states stored in a scene file
 (dgppo_fov_amd/utils/scene.py) instead of seeds -- episodes are rows [offset:epi] of the file, all of its rows when
@@ -97,6 +104,18 @@ def test(args):
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(f"{env.num_agents},{args.epi},{env.max_episode_steps},{env.area_size},{env.params['n_obs']},"
                     f"{safe_mean * 100:.3f},{safe_std * 100:.3f}\n")
+    if args.video and not args.no_video:  # test.py:148-159 of the reference, opt-in and capped here
+        import datetime
+
+        stamp = datetime.datetime.now().strftime("%m%d-%H%M")
+        videos_dir = os.path.join(args.path, "videos", f"{step}")
+        os.makedirs(videos_dir, exist_ok=True)
+        Ta_is_unsafe = (roll.costs >= 0.0).any(dim=-1)  # (epi, T, n)
+        for k, i in list(enumerate(episodes))[:max(args.max_videos, 0)]:
+            rate = (1 - is_unsafe[k].mean()) * 100
+            name = f"n{num_agents}_epi{i:02}_reward{rewards[k]:.3f}_cost{costs[k]:.3f}_sr{rate:.0f}"
+            env.render_video(roll, os.path.join(videos_dir, f"{stamp}_{name}.gif"), Ta_is_unsafe[k], {}, dpi=args.dpi,
+                             episode=k)
     return dict(reward=float(np.mean(rewards)), cost=float(np.mean(costs)), safe_rate=float(safe_mean))
 
 
@@ -104,6 +123,8 @@ def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--path", type=str, required=True)
     parser.add_argument("--no-video", action="store_true", default=False)
+    parser.add_argument("--video", action="store_true", default=False)  # opt-in (the reference: on unless --no-video)
+    parser.add_argument("--max-videos", type=int, default=5)
     parser.add_argument("--epi", type=int, default=None)  # 5 without --scene, every row of the file with it
     parser.add_argument("--scene", type=str, default=None)
     parser.add_argument("--dump-scene", type=str, default=None)
