@@ -1,4 +1,5 @@
-# Builds dgppo_fov_amd/lib/libdgppo_hip.so for gfx950 (MI355X).  `make -j8`.
+# Builds dgppo_fov_amd/lib/libdgppo_hip.so for gfx950 (MI355X).  `make -j16`: one object per csrc/*.hip (env_step.hip,
+# about 2.5 minutes, is the longest).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 CSRC := dgppo_fov_amd/csrc
@@ -7,8 +8,8 @@ OBJ := dgppo_fov_amd/_build
 SRCS := $(wildcard $(CSRC)/*.hip)
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJ)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) include/dgppo_hip.h
-# env kernels must not contract a*b+c into FMA (bit parity with the NumPy oracle): env_step.hip and
-# math32.h carry `#pragma clang fp contract(off)`; the network kernels keep the default (FMA).
+# env kernels must not contract a*b+c into FMA (bit parity with the NumPy oracle): env_step.hip, math32.h and
+# noise.h carry `#pragma clang fp contract(off)`; the network kernels keep the default (FMA).
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Iinclude
 
 all: $(OUT)/libdgppo_hip.so
@@ -21,43 +22,30 @@ $(OUT)/libdgppo_hip.so: $(OBJS)
 	@mkdir -p $(OUT)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS)
 
-# diagnostic library with the persistent rollout's phase timers (scripts/env_stamps.py; DGPPO_HIP_LIB points at it)
-STAMP_OBJS := $(filter-out $(OBJ)/env_step.o,$(OBJS)) $(OBJ)/env_step_stamps.o
-$(OBJ)/env_step_stamps.o: $(CSRC)/env_step.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DDGPPO_ENV_STAMPS -c $< -o $@
-stamps: $(STAMP_OBJS)
-	@mkdir -p $(OUT)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(OUT)/libdgppo_hip_stamps.so $(STAMP_OBJS)
-
-# diagnostic library with every env-graph store dropped from the wave kernels (timing experiments only)
-NOSTORE_OBJS := $(filter-out $(OBJ)/env_step.o,$(OBJS)) $(OBJ)/env_step_nostore.o
-$(OBJ)/env_step_nostore.o: $(CSRC)/env_step.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DDGPPO_DIAG_NOSTORE -c $< -o $@
-nostore: $(NOSTORE_OBJS)
-	@mkdir -p $(OUT)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(OUT)/libdgppo_hip_nostore.so $(NOSTORE_OBJS)
-
 clean:
 	rm -rf $(OBJ) $(OUT)/libdgppo_hip.so
 
-.PHONY: all clean stamps nostore
-
-# diagnostic library with the fused policy step's phase timestamps (scripts/policy_probe.py; DGPPO_HIP_LIB points at it)
-PROBE_OBJS := $(filter-out $(OBJ)/policy.o,$(OBJS)) $(OBJ)/policy_probe.o
-$(OBJ)/policy_probe.o: $(CSRC)/policy.hip $(HDRS)
+# Diagnostic libraries (DGPPO_HIP_LIB points at one): $(call diag_lib,NAME,FLAGS,UNITS) makes target NAME, which
+# recompiles UNITS with FLAGS into _build/UNIT_NAME.o and links them with every other in-tree object into
+# lib/libdgppo_hip_NAME.so.
+define diag_lib
+$(1)_OBJS := $$(filter-out $$(patsubst %,$(OBJ)/%.o,$(3)),$$(OBJS)) $$(patsubst %,$(OBJ)/%_$(1).o,$(3))
+$(OBJ)/%_$(1).o: $(CSRC)/%.hip $$(HDRS)
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DPOLICY_PROBE -c $< -o $@
-probe: $(PROBE_OBJS)
+	$$(HIPCC) $$(HIPFLAGS) $(2) -c $$< -o $$@
+$(1): $$($(1)_OBJS)
 	@mkdir -p $(OUT)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(OUT)/libdgppo_hip_probe.so $(PROBE_OBJS)
+	$$(HIPCC) --offload-arch=$$(ARCH) -shared -o $(OUT)/libdgppo_hip_$(1).so $$($(1)_OBJS)
+.PHONY: $(1)
+endef
 
-# register-form policy step at 4 waves per SIMD instead of the default 3 (A/B: DGPPO_HIP_LIB=dgppo_fov_amd/lib/libdgppo_hip_w4.so)
-W4_OBJS := $(filter-out $(OBJ)/policy.o,$(OBJS)) $(OBJ)/policy_w4.o
-$(OBJ)/policy_w4.o: $(CSRC)/policy.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DPOLICY_REG_WAVES=4 -c $< -o $@
-w4: $(W4_OBJS)
-	@mkdir -p $(OUT)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $(OUT)/libdgppo_hip_w4.so $(W4_OBJS)
+# the env kernels' phase timers: block step (scripts/block_stamps.py) and persistent wave rollout (scripts/env_stamps.py)
+$(eval $(call diag_lib,stamps,-DDGPPO_ENV_STAMPS,env_step))
+# every env-graph store dropped from the wave kernels (timing experiments only)
+$(eval $(call diag_lib,nostore,-DDGPPO_DIAG_NOSTORE,env_step))
+# the fused policy step's phase timestamps (scripts/policy_probe.py)
+$(eval $(call diag_lib,probe,-DPOLICY_PROBE,policy))
+# register-form policy step at 4 waves per SIMD instead of the default 3 (A/B against the in-tree library)
+$(eval $(call diag_lib,w4,-DPOLICY_REG_WAVES=4,policy))
+
+.PHONY: all clean

@@ -29,6 +29,7 @@
 #include "vmas.h"
 
 #pragma clang fp contract(off)
+#pragma clang diagnostic ignored "-Wbitwise-instead-of-logical"  // branch-free predicates on purpose
 
 namespace dgppo {
 
@@ -550,7 +551,7 @@ __device__ __forceinline__ void lidar_scan(const D& d, const float* ray_dirs, fl
         r2 = fmaxf(r2, dx * dx + dy * dy);
       }
       const float rh = __builtin_amdgcn_sqrtf(r2) * 1.0001f + 1e-6f;
-      rho[o] = elig & (rh <= 0.5f) ? rh : -1.0f;
+      rho[o] = (elig & (rh <= 0.5f)) ? rh : -1.0f;
       unsafe[o] = 0u;
     }
     for (int p = tid; p < n * R; p += nthr) aenc[p] = 0x49742400u + 1u;  // enc(1e6f)
@@ -1072,7 +1073,6 @@ __device__ __forceinline__ bool rect_inside0(const float* rec, float px, float p
 // (~65 of 768 per env at the bench distribution) go to a compacted work list, pooled over the 4 envs
 // of a workgroup, and run the exact per-edge arithmetic (raytrace_nodiv / rect_raytrace), combined
 // per ray with an LDS atomic min on an order-preserving encoding (NaN wins, as jnp.min).
-#pragma clang diagnostic ignored "-Wbitwise-instead-of-logical"  // branch-free predicates on purpose
 constexpr int kOmniSD = 7, kOmniED = 10, kOmniNC = 5;  // LidarOmniTarget state / edge width, costs
 // 16-byte state rows (SD = 4) stored one float4 per lane instead of one dword per lane and column (A/B builds:
 // -DDGPPO_ENV_ST4=0 restores the dword stores)
@@ -3409,6 +3409,16 @@ __global__ __launch_bounds__(kT) void graph_kernel(dgppo_env_cfg cfg, dgppo_env_
   __syncthreads();
   graph_of_staged_rows_var<ENGINE>(cfg, io, d, cv, lds, env);
 }
+
+// the one launch of the step, reset and graph kernels: LDS size, the 64 KB check, the MPE or the LIDAR instance
+template <class IO>
+static int launch(void (*mpe)(dgppo_env_cfg, IO), void (*lidar)(dgppo_env_cfg, IO), const dgppo_env_cfg& c,
+                  const IO& io, hipStream_t s) {
+  const size_t sh = lds_floats(c) * sizeof(float);
+  if (sh > 64 * 1024) return DGPPO_EINVAL;
+  hipLaunchKernelGGL(c.engine == DGPPO_ENGINE_MPE ? mpe : lidar, dim3((unsigned)io.n_env), dim3(kT), sh, s, c, io);
+  return (int)hipGetLastError();
+}
 }  // namespace var
 
 // ---- host dispatch --------------------------------------------------------------------------
@@ -3450,142 +3460,106 @@ static bool wave_step_enabled() {
 }
 
 // ---- launch helpers ---------------------------------------------------------------------------
-template <int ENGINE, int GOAL, int SD, int BLOCK, int NA, int NO, int NR, int NK>
-static void launch_step(const dgppo_env_cfg& c, const dgppo_env_step_io& io, size_t shmem, hipStream_t s) {
-  hipLaunchKernelGGL((env_step_kernel<ENGINE, GOAL, SD, BLOCK, NA, NO, NR, NK>), dim3((unsigned)io.n_env),
-                     dim3(BLOCK), shmem, s, c, io);
+template <int E, int G, int S>
+struct EnvTag {
+  static constexpr int ENGINE = E, GOAL = G, SD = S;
+};
+
+// The one mapping (cfg.engine, cfg.goal_mode) of a validated cfg -> f(EnvTag<ENGINE, GOAL, SD>{}).  OMNI exists with
+// GOAL_TARGET only (validate).  A family without kernels for an engine (block step / rollout: OMNI; wave Lidar:
+// MPE) discards that tag with `if constexpr`, so it instantiates nothing for it; the entry points never send it there.
+template <class F>
+static inline void visit_engine_goal(const dgppo_env_cfg& c, F&& f) {
+  const bool spread = c.goal_mode == DGPPO_GOAL_SPREAD;
+  switch (c.engine) {
+    case DGPPO_ENGINE_MPE:
+      return spread ? f(EnvTag<DGPPO_ENGINE_MPE, DGPPO_GOAL_SPREAD, 4>{}) : f(EnvTag<DGPPO_ENGINE_MPE, DGPPO_GOAL_TARGET, 4>{});
+    case DGPPO_ENGINE_BICYCLE:
+      return spread ? f(EnvTag<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>{})
+                    : f(EnvTag<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>{});
+    case DGPPO_ENGINE_OMNI:
+      return f(EnvTag<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>{});
+    default:
+      return spread ? f(EnvTag<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>{})
+                    : f(EnvTag<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>{});
+  }
 }
 
-template <int ENGINE, int GOAL, int SD, int BLOCK, int NA, int NO, int NR, int NK>
-static void launch_rollout_block(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, size_t shmem, hipStream_t s,
-                                 int stage) {
-  hipLaunchKernelGGL((env_rollout_block_kernel<ENGINE, GOAL, SD, BLOCK, NA, NO, NR, NK>), dim3((unsigned)r.step.n_env),
-                     dim3(BLOCK), shmem, s, c, r, stage);
-}
+template <int B, int A, int O, int R, int K>
+struct SizeTag {
+  static constexpr int BLOCK = B, NA = A, NO = O, NR = R, NK = K;
+};
 
-// the same compile-time size selection as dispatch_step_sized
-template <int ENGINE, int GOAL, int SD>
-static void dispatch_rollout_block_sized(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, size_t shmem,
-                                         hipStream_t s, int stage) {
+// cfg sizes -> f(SizeTag<BLOCK, NA, NO, NR, NK>{}), shared by the block step and rollout: compile-time sizes for the
+// BASELINE.json configs, else run-time sizes (0 / -1) at 256 or 128 threads
+template <int ENGINE, class F>
+static void visit_sizes(const dgppo_env_cfg& c, F&& f) {
   const int n = c.n_agents, O = c.n_obs, R = c.n_rays, k = c.top_k;
   if (ENGINE == DGPPO_ENGINE_MPE) {
-    if (n == 3 && O == 3) return launch_rollout_block<ENGINE, GOAL, SD, 64, 3, 3, 0, 0>(c, r, shmem, s, stage);
-    if (n == 3 && O == 0) return launch_rollout_block<ENGINE, GOAL, SD, 64, 3, 0, 0, 0>(c, r, shmem, s, stage);
-    return launch_rollout_block<ENGINE, GOAL, SD, 64, 0, -1, 0, 0>(c, r, shmem, s, stage);
+    if (n == 3 && O == 3) return f(SizeTag<64, 3, 3, 0, 0>{});
+    if (n == 3 && O == 0) return f(SizeTag<64, 3, 0, 0, 0>{});
+    return f(SizeTag<64, 0, -1, 0, 0>{});
   }
   if (R == 32 && k == 8) {
-    if (n == 8 && O == 3) return launch_rollout_block<ENGINE, GOAL, SD, 256, 8, 3, 32, 8>(c, r, shmem, s, stage);
-    if (n == 32 && O == 8) return launch_rollout_block<ENGINE, GOAL, SD, 256, 32, 8, 32, 8>(c, r, shmem, s, stage);
+    if (n == 8 && O == 3) return f(SizeTag<256, 8, 3, 32, 8>{});
+    if (n == 32 && O == 8) return f(SizeTag<256, 32, 8, 32, 8>{});
   }
-  if (n * R >= 256) return launch_rollout_block<ENGINE, GOAL, SD, 256, 0, -1, 0, 0>(c, r, shmem, s, stage);
-  return launch_rollout_block<ENGINE, GOAL, SD, 128, 0, -1, 0, 0>(c, r, shmem, s, stage);
+  if (n * R >= 256) return f(SizeTag<256, 0, -1, 0, 0>{});
+  return f(SizeTag<128, 0, -1, 0, 0>{});
+}
+
+static void dispatch_step(const dgppo_env_cfg& c, const dgppo_env_step_io& io, size_t shmem, hipStream_t s) {
+  visit_engine_goal(c, [&](auto e) {
+    using E = decltype(e);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_OMNI)
+      visit_sizes<E::ENGINE>(c, [&](auto z) {
+        using Z = decltype(z);
+        hipLaunchKernelGGL((env_step_kernel<E::ENGINE, E::GOAL, E::SD, Z::BLOCK, Z::NA, Z::NO, Z::NR, Z::NK>),
+                           dim3((unsigned)io.n_env), dim3(Z::BLOCK), shmem, s, c, io);
+      });
+  });
 }
 
 static void dispatch_rollout_block(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, size_t shmem, hipStream_t s,
                                    int stage) {
-  const bool spread = c.goal_mode == DGPPO_GOAL_SPREAD;
-  switch (c.engine) {
-    case DGPPO_ENGINE_MPE:
-      return spread ? dispatch_rollout_block_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_SPREAD, 4>(c, r, shmem, s, stage)
-                    : dispatch_rollout_block_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_TARGET, 4>(c, r, shmem, s, stage);
-    case DGPPO_ENGINE_BICYCLE:
-      return spread ? dispatch_rollout_block_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(c, r, shmem, s, stage)
-                    : dispatch_rollout_block_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(c, r, shmem, s, stage);
-    default:
-      return spread ? dispatch_rollout_block_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(c, r, shmem, s, stage)
-                    : dispatch_rollout_block_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(c, r, shmem, s, stage);
-  }
-}
-
-template <int ENGINE, int GOAL, int SD>
-static void dispatch_step_sized(const dgppo_env_cfg& c, const dgppo_env_step_io& io, size_t shmem, hipStream_t s) {
-  const int n = c.n_agents, O = c.n_obs, R = c.n_rays, k = c.top_k;
-  if (ENGINE == DGPPO_ENGINE_MPE) {
-    if (n == 3 && O == 3) return launch_step<ENGINE, GOAL, SD, 64, 3, 3, 0, 0>(c, io, shmem, s);
-    if (n == 3 && O == 0) return launch_step<ENGINE, GOAL, SD, 64, 3, 0, 0, 0>(c, io, shmem, s);
-    return launch_step<ENGINE, GOAL, SD, 64, 0, -1, 0, 0>(c, io, shmem, s);
-  }
-  if (R == 32 && k == 8) {  // the BASELINE.json Lidar configs: compile-time sizes
-    if (n == 8 && O == 3) return launch_step<ENGINE, GOAL, SD, 256, 8, 3, 32, 8>(c, io, shmem, s);
-    if (n == 32 && O == 8) return launch_step<ENGINE, GOAL, SD, 256, 32, 8, 32, 8>(c, io, shmem, s);
-  }
-  if (n * R >= 256) return launch_step<ENGINE, GOAL, SD, 256, 0, -1, 0, 0>(c, io, shmem, s);
-  return launch_step<ENGINE, GOAL, SD, 128, 0, -1, 0, 0>(c, io, shmem, s);
-}
-
-static void dispatch_step(const dgppo_env_cfg& c, const dgppo_env_step_io& io, size_t shmem, hipStream_t s) {
-  const bool spread = c.goal_mode == DGPPO_GOAL_SPREAD;
-  switch (c.engine) {
-    case DGPPO_ENGINE_MPE:
-      return spread ? dispatch_step_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s)
-                    : dispatch_step_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s);
-    case DGPPO_ENGINE_BICYCLE:
-      return spread ? dispatch_step_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(c, io, shmem, s)
-                    : dispatch_step_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(c, io, shmem, s);
-    default:
-      return spread ? dispatch_step_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s)
-                    : dispatch_step_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s);
-  }
-}
-
-template <int ENGINE, int GOAL, int SD>
-static void dispatch_reset_sized(const dgppo_env_cfg& c, const dgppo_env_reset_io& io, size_t shmem, hipStream_t s,
-                                 int states_only) {
-  const dim3 grid((unsigned)io.n_env);
-  // MPE and states-only resets need one wave (sampler; no workgroup ray cast): 64 threads, so many more
-  // envs are resident per CU and their sequential sampling latencies overlap
-  if (ENGINE == DGPPO_ENGINE_MPE || states_only)
-    hipLaunchKernelGGL((env_reset_kernel<ENGINE, GOAL, SD, 64>), grid, dim3(64), shmem, s, c, io, states_only);
-  else if (c.n_agents * c.n_rays >= 256)
-    hipLaunchKernelGGL((env_reset_kernel<ENGINE, GOAL, SD, 256>), grid, dim3(256), shmem, s, c, io, states_only);
-  else
-    hipLaunchKernelGGL((env_reset_kernel<ENGINE, GOAL, SD, 128>), grid, dim3(128), shmem, s, c, io, states_only);
+  visit_engine_goal(c, [&](auto e) {
+    using E = decltype(e);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_OMNI)
+      visit_sizes<E::ENGINE>(c, [&](auto z) {
+        using Z = decltype(z);
+        hipLaunchKernelGGL((env_rollout_block_kernel<E::ENGINE, E::GOAL, E::SD, Z::BLOCK, Z::NA, Z::NO, Z::NR, Z::NK>),
+                           dim3((unsigned)r.step.n_env), dim3(Z::BLOCK), shmem, s, c, r, stage);
+      });
+  });
 }
 
 static void dispatch_reset(const dgppo_env_cfg& c, const dgppo_env_reset_io& io, size_t shmem, hipStream_t s,
-                           int so) {
-  const bool spread = c.goal_mode == DGPPO_GOAL_SPREAD;
-  switch (c.engine) {
-    case DGPPO_ENGINE_MPE:
-      return spread ? dispatch_reset_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s, so)
-                    : dispatch_reset_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s, so);
-    case DGPPO_ENGINE_BICYCLE:
-      return spread ? dispatch_reset_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(c, io, shmem, s, so)
-                    : dispatch_reset_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(c, io, shmem, s, so);
-    case DGPPO_ENGINE_OMNI:
-      return dispatch_reset_sized<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>(c, io, shmem, s, so);
-    default:
-      return spread ? dispatch_reset_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s, so)
-                    : dispatch_reset_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s, so);
-  }
-}
-
-template <int ENGINE, int GOAL, int SD>
-static void dispatch_graph_sized(const dgppo_env_cfg& c, const dgppo_env_graph_io& io, size_t shmem, hipStream_t s) {
+                           int states_only) {
   const dim3 grid((unsigned)io.n_env);
-  if (ENGINE == DGPPO_ENGINE_MPE)  // no ray cast: one wave
-    hipLaunchKernelGGL((env_graph_kernel<ENGINE, GOAL, SD, 64>), grid, dim3(64), shmem, s, c, io);
-  else if (c.n_agents * c.n_rays >= 256)
-    hipLaunchKernelGGL((env_graph_kernel<ENGINE, GOAL, SD, 256>), grid, dim3(256), shmem, s, c, io);
-  else
-    hipLaunchKernelGGL((env_graph_kernel<ENGINE, GOAL, SD, 128>), grid, dim3(128), shmem, s, c, io);
+  visit_engine_goal(c, [&](auto e) {
+    using E = decltype(e);
+    // MPE and states-only resets need one wave (sampler; no workgroup ray cast): 64 threads, so many more
+    // envs are resident per CU and their sequential sampling latencies overlap
+    if (E::ENGINE == DGPPO_ENGINE_MPE || states_only)
+      hipLaunchKernelGGL((env_reset_kernel<E::ENGINE, E::GOAL, E::SD, 64>), grid, dim3(64), shmem, s, c, io, states_only);
+    else if (c.n_agents * c.n_rays >= 256)
+      hipLaunchKernelGGL((env_reset_kernel<E::ENGINE, E::GOAL, E::SD, 256>), grid, dim3(256), shmem, s, c, io, states_only);
+    else
+      hipLaunchKernelGGL((env_reset_kernel<E::ENGINE, E::GOAL, E::SD, 128>), grid, dim3(128), shmem, s, c, io, states_only);
+  });
 }
 
 static void dispatch_graph(const dgppo_env_cfg& c, const dgppo_env_graph_io& io, size_t shmem, hipStream_t s) {
-  const bool spread = c.goal_mode == DGPPO_GOAL_SPREAD;
-  switch (c.engine) {
-    case DGPPO_ENGINE_MPE:
-      return spread ? dispatch_graph_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s)
-                    : dispatch_graph_sized<DGPPO_ENGINE_MPE, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s);
-    case DGPPO_ENGINE_BICYCLE:
-      return spread ? dispatch_graph_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(c, io, shmem, s)
-                    : dispatch_graph_sized<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(c, io, shmem, s);
-    case DGPPO_ENGINE_OMNI:
-      return dispatch_graph_sized<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>(c, io, shmem, s);
-    default:
-      return spread ? dispatch_graph_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(c, io, shmem, s)
-                    : dispatch_graph_sized<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(c, io, shmem, s);
-  }
+  const dim3 grid((unsigned)io.n_env);
+  visit_engine_goal(c, [&](auto e) {
+    using E = decltype(e);
+    if (E::ENGINE == DGPPO_ENGINE_MPE)  // no ray cast: one wave
+      hipLaunchKernelGGL((env_graph_kernel<E::ENGINE, E::GOAL, E::SD, 64>), grid, dim3(64), shmem, s, c, io);
+    else if (c.n_agents * c.n_rays >= 256)
+      hipLaunchKernelGGL((env_graph_kernel<E::ENGINE, E::GOAL, E::SD, 256>), grid, dim3(256), shmem, s, c, io);
+    else
+      hipLaunchKernelGGL((env_graph_kernel<E::ENGINE, E::GOAL, E::SD, 128>), grid, dim3(128), shmem, s, c, io);
+  });
 }
 
 }  // namespace dgppo
@@ -3594,8 +3568,10 @@ using namespace dgppo;
 
 extern "C" int dgppo_abi_version(void) { return DGPPO_ABI_VERSION; }
 
+#define DGPPO_STR_(x) #x
+#define DGPPO_STR(x) DGPPO_STR_(x)
 extern "C" const char* dgppo_build_info(void) {
-  return "libdgppo_hip gfx950 abi=" "1" " env_step+env_reset (fp-contract=off)";
+  return "libdgppo_hip gfx950 abi=" DGPPO_STR(DGPPO_ABI_VERSION) " env_step+env_reset (fp-contract=off)";
 }
 
 // smallest fp32 x with sqrtf(x) >= r (IEEE sqrt is correctly rounded and monotone, so for every
@@ -3698,67 +3674,6 @@ extern "C" int dgppo_env_set_step_kernel(int mode) {
   return prev;
 }
 
-static bool wave_bufs_aligned(const dgppo_env_cfg* cfg, const float* edges, int64_t edges_stride, int64_t t_edges,
-                              const float* states, int64_t states_stride, int64_t t_states);
-
-extern "C" int dgppo_env_step(const dgppo_env_cfg* cfg, const dgppo_env_step_io* io, void* stream) {
-  if (validate(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
-  if (vmas::is_vmas(cfg)) return vmas::step(cfg, io, stream);
-  if (io->n_env == 0) return 0;
-  if (!io->states || !io->action || !io->nodes || !io->edges || !io->out_states || !io->receivers ||
-      !io->senders || !io->reward || !io->cost)
-    return DGPPO_EINVAL;
-  const bool lidar = cfg->engine != DGPPO_ENGINE_MPE && cfg->n_obs > 0;
-  if (lidar && (!io->obstacles || !io->ray_dirs)) return DGPPO_EINVAL;
-  if (cfg->variant != DGPPO_VARIANT_NONE) {
-    const size_t sh = var::lds_floats(*cfg) * sizeof(float);
-    if (sh > 64 * 1024) return DGPPO_EINVAL;
-    if (cfg->engine == DGPPO_ENGINE_MPE)
-      hipLaunchKernelGGL(var::step_kernel<DGPPO_ENGINE_MPE>, dim3((unsigned)io->n_env), dim3(var::kT), sh,
-                         (hipStream_t)stream, *cfg, *io);
-    else
-      hipLaunchKernelGGL(var::step_kernel<DGPPO_ENGINE_LIDAR>, dim3((unsigned)io->n_env), dim3(var::kT), sh,
-                         (hipStream_t)stream, *cfg, *io);
-    return (int)hipGetLastError();
-  }
-  const bool wave_shape = lidar && cfg->n_agents == wv::NA && cfg->n_rays == wv::NR && cfg->top_k == wv::NK &&
-                          cfg->n_obs == 3 && wave_step_enabled() &&
-                          wave_bufs_aligned(cfg, io->edges, io->edges_stride, 0, io->out_states, io->out_states_stride, 0);
-  if (cfg->engine == DGPPO_ENGINE_OMNI && wave_shape) {
-    const size_t sh = 4 * sizeof(float) * wv::Carve<kOmniSD, 3>::total;
-    hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD, 3>),
-                       dim3((unsigned)((io->n_env + 3) / 4)), dim3(256), sh, (hipStream_t)stream, *cfg, *io);
-    return (int)hipGetLastError();
-  }
-  if (cfg->engine == DGPPO_ENGINE_OMNI) {
-    const size_t sh = omni_step_lds_bytes(*cfg);
-    if (sh > 64 * 1024) return DGPPO_EINVAL;
-    hipLaunchKernelGGL(omni_step_kernel<256>, dim3((unsigned)io->n_env), dim3(256), sh, (hipStream_t)stream, *cfg,
-                       *io);
-    return (int)hipGetLastError();
-  }
-  if (wave_shape) {
-    const dim3 grid((unsigned)((io->n_env + 3) / 4)), block(256);
-    const hipStream_t s = (hipStream_t)stream;
-    const bool spread = cfg->goal_mode == DGPPO_GOAL_SPREAD;
-    if (cfg->engine == DGPPO_ENGINE_BICYCLE) {
-      const size_t sh = 4 * sizeof(float) * wv::Carve<5, 3>::total;
-      if (spread) hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5, 3>), grid, block, sh, s, *cfg, *io);
-      else hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5, 3>), grid, block, sh, s, *cfg, *io);
-    } else {
-      const size_t sh = 4 * sizeof(float) * wv::Carve<4, 3>::total;
-      if (spread) hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4, 3>), grid, block, sh, s, *cfg, *io);
-      else hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4, 3>), grid, block, sh, s, *cfg, *io);
-    }
-    return (int)hipGetLastError();
-  }
-  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k,
-                 cfg->engine != DGPPO_ENGINE_MPE);
-  const size_t shmem = (size_t)cv.total * sizeof(float);
-  dispatch_step(*cfg, *io, shmem, (hipStream_t)stream);
-  return (int)hipGetLastError();
-}
-
 // the wave kernels store edge rows as float4 (4-wide) / float2 (LidarOmniTarget's 10-wide) and 4-wide state rows
 // as float4: those buffers, their per-env strides and (rollouts) their per-step strides must keep that alignment,
 // else the generic kernels run
@@ -3779,32 +3694,107 @@ static bool wave_config(const dgppo_env_cfg* cfg, const float* edges, int64_t ed
          wave_bufs_aligned(cfg, edges, edges_stride, t_edges, states, states_stride, t_states);
 }
 
+// the MPE wave rollout's config (its buffer alignment is the caller's to check)
+static bool mpe_wave_config(const dgppo_env_cfg* cfg) {
+  return cfg->engine == DGPPO_ENGINE_MPE && cfg->variant == DGPPO_VARIANT_NONE && cfg->n_agents == wv::mpew::NA &&
+         cfg->n_obs == wv::mpew::NO && wave_step_enabled();
+}
+
+// the wave step / REBUILD / graph kernels: 4 envs per 256-thread workgroup (MPE has none: its tag is discarded)
+template <int SD>
+constexpr size_t kWaveStepLds = 4 * sizeof(float) * wv::Carve<SD, 3>::total;
+static dim3 wave_step_grid(int64_t n_env) { return dim3((unsigned)((n_env + 3) / 4)); }
+
+static void launch_wave_step(const dgppo_env_cfg* cfg, const dgppo_env_step_io& io, hipStream_t s) {
+  visit_engine_goal(*cfg, [&](auto e) {
+    using E = decltype(e);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
+      hipLaunchKernelGGL((wv::lidar_step_wave_kernel<E::ENGINE, E::GOAL, E::SD, 3>), wave_step_grid(io.n_env), dim3(256),
+                         kWaveStepLds<E::SD>, s, *cfg, io);
+  });
+}
+
 // the initial graph of sampled agent / goal rows and obstacles: the wave step kernel in REBUILD mode, in place
 static void launch_rebuild(const dgppo_env_cfg* cfg, const dgppo_env_step_io& st, hipStream_t s) {
-  const dim3 grid((unsigned)((st.n_env + 3) / 4)), block(256);
-  const bool spread = cfg->goal_mode == DGPPO_GOAL_SPREAD;
-  if (cfg->engine == DGPPO_ENGINE_OMNI) {
-    const size_t sh = 4 * sizeof(float) * wv::Carve<kOmniSD, 3>::total;
-    hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD, 3, true>), grid, block,
-                       sh, s, *cfg, st);
-  } else if (cfg->engine == DGPPO_ENGINE_BICYCLE) {
-    const size_t sh = 4 * sizeof(float) * wv::Carve<5, 3>::total;
-    if (spread)
-      hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5, 3, true>), grid, block,
-                         sh, s, *cfg, st);
-    else
-      hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5, 3, true>), grid, block,
-                         sh, s, *cfg, st);
-  } else {
-    const size_t sh = 4 * sizeof(float) * wv::Carve<4, 3>::total;
-    if (spread)
-      hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4, 3, true>), grid, block,
-                         sh, s, *cfg, st);
-    else
-      hipLaunchKernelGGL((wv::lidar_step_wave_kernel<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4, 3, true>), grid, block,
-                         sh, s, *cfg, st);
-  }
+  visit_engine_goal(*cfg, [&](auto e) {
+    using E = decltype(e);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
+      hipLaunchKernelGGL((wv::lidar_step_wave_kernel<E::ENGINE, E::GOAL, E::SD, 3, true>), wave_step_grid(st.n_env),
+                         dim3(256), kWaveStepLds<E::SD>, s, *cfg, st);
+  });
 }
+
+// The step io of a REBUILD / graph launch of the wave step kernel: `rows` (and obstacles) in, `io`'s graph buffers
+// out.  The action is read, never used.
+template <class IO>
+static dgppo_env_step_io rebuild_io(const IO& io, const float* rows, int64_t rows_stride, const float* obstacles,
+                                    int64_t obstacles_stride) {
+  dgppo_env_step_io st{};
+  st.states = rows;
+  st.states_stride = rows_stride;
+  st.obstacles = obstacles;
+  st.obstacles_stride = obstacles_stride;
+  st.action = rows;
+  st.action_stride = rows_stride;
+  st.ray_dirs = io.ray_dirs;
+  st.nodes = io.nodes;
+  st.nodes_stride = io.nodes_stride;
+  st.edges = io.edges;
+  st.edges_stride = io.edges_stride;
+  st.out_states = io.out_states;
+  st.out_states_stride = io.out_states_stride;
+  st.receivers = io.receivers;
+  st.senders = io.senders;
+  st.edge_index_stride = io.edge_index_stride;
+  st.n_env = io.n_env;
+  return st;
+}
+
+// The step io of time t of a rollout io: step t reads graph t's rows and action t, writes graph t + 1, reward[t],
+// cost[t].  (env_rollout_block_kernel keeps its written-out copy: through this helper its scalar code comes out
+// differently.)
+__host__ __device__ __forceinline__ dgppo_env_step_io step_io_at(const dgppo_env_rollout_io& r, int t) {
+  dgppo_env_step_io q = r.step;
+  q.states = r.step.out_states + t * r.t_states;
+  q.action = r.step.action + t * r.t_action;
+  q.nodes = r.step.nodes + (t + 1) * r.t_nodes;
+  q.edges = r.step.edges + (t + 1) * r.t_edges;
+  q.out_states = r.step.out_states + (t + 1) * r.t_states;
+  q.receivers = r.step.receivers + (t + 1) * r.t_index;
+  q.senders = r.step.senders + (t + 1) * r.t_index;
+  q.reward = r.step.reward + t * r.t_reward;
+  q.cost = r.step.cost + t * r.t_cost;
+  return q;
+}
+extern "C" int dgppo_env_step(const dgppo_env_cfg* cfg, const dgppo_env_step_io* io, void* stream) {
+  if (validate(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (vmas::is_vmas(cfg)) return vmas::step(cfg, io, stream);
+  if (io->n_env == 0) return 0;
+  if (!io->states || !io->action || !io->nodes || !io->edges || !io->out_states || !io->receivers ||
+      !io->senders || !io->reward || !io->cost)
+    return DGPPO_EINVAL;
+  const bool lidar = cfg->engine != DGPPO_ENGINE_MPE && cfg->n_obs > 0;
+  if (lidar && (!io->obstacles || !io->ray_dirs)) return DGPPO_EINVAL;
+  const hipStream_t s = (hipStream_t)stream;
+  if (cfg->variant != DGPPO_VARIANT_NONE)
+    return var::launch(var::step_kernel<DGPPO_ENGINE_MPE>, var::step_kernel<DGPPO_ENGINE_LIDAR>, *cfg, *io, s);
+  if (wave_config(cfg, io->edges, io->edges_stride, 0, io->out_states, io->out_states_stride, 0)) {
+    launch_wave_step(cfg, *io, s);
+    return (int)hipGetLastError();
+  }
+  if (cfg->engine == DGPPO_ENGINE_OMNI) {
+    const size_t sh = omni_step_lds_bytes(*cfg);
+    if (sh > 64 * 1024) return DGPPO_EINVAL;
+    hipLaunchKernelGGL(omni_step_kernel<256>, dim3((unsigned)io->n_env), dim3(256), sh, s, *cfg, *io);
+    return (int)hipGetLastError();
+  }
+  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k,
+                 cfg->engine != DGPPO_ENGINE_MPE);
+  const size_t shmem = (size_t)cv.total * sizeof(float);
+  dispatch_step(*cfg, *io, shmem, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+
 
 extern "C" int dgppo_env_reset_states(const dgppo_env_cfg* cfg, const dgppo_env_reset_io* io, void* stream) {
   if (validate(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
@@ -3882,12 +3872,10 @@ extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollo
   if (lidar && (!io.obstacles || !io.ray_dirs)) return DGPPO_EINVAL;
   const hipStream_t s = (hipStream_t)stream;
   if (wave_config(cfg, io.edges, io.edges_stride, r->t_edges, io.out_states, io.out_states_stride, r->t_states)) {
-    const bool spread = cfg->goal_mode == DGPPO_GOAL_SPREAD;
-    if (cfg->engine == DGPPO_ENGINE_OMNI) launch_rollout<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>(*cfg, *r, s);
-    else if (cfg->engine == DGPPO_ENGINE_BICYCLE && spread) launch_rollout<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(*cfg, *r, s);
-    else if (cfg->engine == DGPPO_ENGINE_BICYCLE) launch_rollout<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(*cfg, *r, s);
-    else if (spread) launch_rollout<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(*cfg, *r, s);
-    else launch_rollout<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(*cfg, *r, s);
+    visit_engine_goal(*cfg, [&](auto e) {
+      using E = decltype(e);
+      if constexpr (E::ENGINE != DGPPO_ENGINE_MPE) launch_rollout<E::ENGINE, E::GOAL, E::SD>(*cfg, *r, s);
+    });
     return (int)hipGetLastError();
   }
   // other configs: rebuild_first: a states-only reset (dgppo_env_reset_states) left graph 0 unbuilt when the
@@ -3905,8 +3893,7 @@ extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollo
     const char* e = getenv("DGPPO_MPE_WAVE");
     return !(e && atoi(e) == 0);
   }();
-  if (block_rollout && mpe_wave && r->T > 0 && cfg->engine == DGPPO_ENGINE_MPE && cfg->variant == DGPPO_VARIANT_NONE &&
-      cfg->n_agents == wv::mpew::NA && cfg->n_obs == wv::mpew::NO && wave_step_enabled() &&
+  if (block_rollout && mpe_wave && r->T > 0 && mpe_wave_config(cfg) &&
       (reinterpret_cast<uintptr_t>(io.edges) % 16u) == 0 && io.edges_stride % 4 == 0 && r->t_edges % 4 == 0) {
     const size_t sh = 4 * sizeof(float) * wv::mpew::TOTAL;
     const dim3 grid((unsigned)((io.n_env + 3) / 4));
@@ -3930,16 +3917,7 @@ extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollo
     return (int)hipGetLastError();
   }
   for (int t = 0; t < r->T; ++t) {
-    dgppo_env_step_io q = io;
-    q.states = io.out_states + t * r->t_states;
-    q.action = io.action + t * r->t_action;
-    q.nodes = io.nodes + (t + 1) * r->t_nodes;
-    q.edges = io.edges + (t + 1) * r->t_edges;
-    q.out_states = io.out_states + (t + 1) * r->t_states;
-    q.receivers = io.receivers + (t + 1) * r->t_index;
-    q.senders = io.senders + (t + 1) * r->t_index;
-    q.reward = io.reward + t * r->t_reward;
-    q.cost = io.cost + t * r->t_cost;
+    const dgppo_env_step_io q = step_io_at(*r, t);
     const int rc = dgppo_env_step(cfg, &q, stream);
     if (rc) return rc;
   }
@@ -3954,17 +3932,8 @@ extern "C" int dgppo_env_reset(const dgppo_env_cfg* cfg, const dgppo_env_reset_i
   const bool lidar = cfg->engine != DGPPO_ENGINE_MPE && cfg->n_obs > 0;
   if (lidar && (!io->obstacles || !io->ray_dirs)) return DGPPO_EINVAL;
   const hipStream_t s = (hipStream_t)stream;
-  if (cfg->variant != DGPPO_VARIANT_NONE) {
-    const size_t sh = var::lds_floats(*cfg) * sizeof(float);
-    if (sh > 64 * 1024) return DGPPO_EINVAL;
-    if (cfg->engine == DGPPO_ENGINE_MPE)
-      hipLaunchKernelGGL(var::reset_kernel<DGPPO_ENGINE_MPE>, dim3((unsigned)io->n_env), dim3(var::kT), sh, s, *cfg,
-                         *io);
-    else
-      hipLaunchKernelGGL(var::reset_kernel<DGPPO_ENGINE_LIDAR>, dim3((unsigned)io->n_env), dim3(var::kT), sh, s,
-                         *cfg, *io);
-    return (int)hipGetLastError();
-  }
+  if (cfg->variant != DGPPO_VARIANT_NONE)
+    return var::launch(var::reset_kernel<DGPPO_ENGINE_MPE>, var::reset_kernel<DGPPO_ENGINE_LIDAR>, *cfg, *io, s);
   const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k,
                  cfg->engine != DGPPO_ENGINE_MPE);
   const size_t shmem = ((size_t)cv.total + 2 * kSampTab) * sizeof(float);  // + the sampler's candidate table
@@ -3976,36 +3945,8 @@ extern "C" int dgppo_env_reset(const dgppo_env_cfg* cfg, const dgppo_env_reset_i
   // sampled agent / goal rows and obstacles, then the wave-per-env step kernel in REBUILD mode builds
   // the initial graph from them in place (same LiDAR and graph code as every step)
   dispatch_reset(*cfg, *io, shmem, s, 1);
-  dgppo_env_step_io st{};
-  st.states = io->out_states;
-  st.states_stride = io->out_states_stride;
-  st.obstacles = io->obstacles;
-  st.obstacles_stride = io->obstacles_stride;
-  st.action = io->out_states;  // read, never used in REBUILD
-  st.action_stride = io->out_states_stride;
-  st.ray_dirs = io->ray_dirs;
-  st.nodes = io->nodes;
-  st.nodes_stride = io->nodes_stride;
-  st.edges = io->edges;
-  st.edges_stride = io->edges_stride;
-  st.out_states = io->out_states;
-  st.out_states_stride = io->out_states_stride;
-  st.receivers = io->receivers;
-  st.senders = io->senders;
-  st.edge_index_stride = io->edge_index_stride;
-  st.n_env = io->n_env;
-  launch_rebuild(cfg, st, s);
+  launch_rebuild(cfg, rebuild_io(*io, io->out_states, io->out_states_stride, io->obstacles, io->obstacles_stride), s);
   return (int)hipGetLastError();
-}
-
-// the wave shape's graph of given states: lidar_graph_wave_kernel, launched as launch_rebuild launches the REBUILD step
-template <int ENGINE, int GOAL, int SD>
-static void launch_graph_wave(const dgppo_env_cfg& c, const dgppo_env_step_io& st, const dgppo_env_graph_io& io,
-                              hipStream_t s) {
-  const dim3 grid((unsigned)((st.n_env + 3) / 4)), block(256);
-  const size_t sh = 4 * sizeof(float) * wv::Carve<SD, 3>::total;
-  hipLaunchKernelGGL((wv::lidar_graph_wave_kernel<ENGINE, GOAL, SD, 3>), grid, block, sh, s, c, st, io.goal,
-                     io.goal_stride);
 }
 
 extern "C" int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_graph_io* io, void* stream) {
@@ -4019,42 +3960,17 @@ extern "C" int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_gra
   if (cfg->n_obs > 0 && !io->third) return DGPPO_EINVAL;
   if (lidar && !io->ray_dirs) return DGPPO_EINVAL;
   const hipStream_t s = (hipStream_t)stream;
-  if (cfg->variant != DGPPO_VARIANT_NONE) {
-    const size_t sh = var::lds_floats(*cfg) * sizeof(float);
-    if (sh > 64 * 1024) return DGPPO_EINVAL;
-    if (mpe)
-      hipLaunchKernelGGL(var::graph_kernel<DGPPO_ENGINE_MPE>, dim3((unsigned)io->n_env), dim3(var::kT), sh, s, *cfg,
-                         *io);
-    else
-      hipLaunchKernelGGL(var::graph_kernel<DGPPO_ENGINE_LIDAR>, dim3((unsigned)io->n_env), dim3(var::kT), sh, s, *cfg,
-                         *io);
-    return (int)hipGetLastError();
-  }
+  if (cfg->variant != DGPPO_VARIANT_NONE)
+    return var::launch(var::graph_kernel<DGPPO_ENGINE_MPE>, var::graph_kernel<DGPPO_ENGINE_LIDAR>, *cfg, *io, s);
   if (wave_config(cfg, io->edges, io->edges_stride, 0, io->out_states, io->out_states_stride, 0)) {
-    dgppo_env_step_io st{};
-    st.states = io->agent;  // agent rows only (goal rows: io->goal)
-    st.states_stride = io->agent_stride;
-    st.obstacles = io->third;
-    st.obstacles_stride = io->third_stride;
-    st.action = io->agent;  // read, never used in REBUILD
-    st.action_stride = io->agent_stride;
-    st.ray_dirs = io->ray_dirs;
-    st.nodes = io->nodes;
-    st.nodes_stride = io->nodes_stride;
-    st.edges = io->edges;
-    st.edges_stride = io->edges_stride;
-    st.out_states = io->out_states;
-    st.out_states_stride = io->out_states_stride;
-    st.receivers = io->receivers;
-    st.senders = io->senders;
-    st.edge_index_stride = io->edge_index_stride;
-    st.n_env = io->n_env;
-    const bool spread = cfg->goal_mode == DGPPO_GOAL_SPREAD;
-    if (cfg->engine == DGPPO_ENGINE_OMNI) launch_graph_wave<DGPPO_ENGINE_OMNI, DGPPO_GOAL_TARGET, kOmniSD>(*cfg, st, *io, s);
-    else if (cfg->engine == DGPPO_ENGINE_BICYCLE && spread) launch_graph_wave<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_SPREAD, 5>(*cfg, st, *io, s);
-    else if (cfg->engine == DGPPO_ENGINE_BICYCLE) launch_graph_wave<DGPPO_ENGINE_BICYCLE, DGPPO_GOAL_TARGET, 5>(*cfg, st, *io, s);
-    else if (spread) launch_graph_wave<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_SPREAD, 4>(*cfg, st, *io, s);
-    else launch_graph_wave<DGPPO_ENGINE_LIDAR, DGPPO_GOAL_TARGET, 4>(*cfg, st, *io, s);
+    // agent rows only (goal rows: io->goal)
+    const dgppo_env_step_io st = rebuild_io(*io, io->agent, io->agent_stride, io->third, io->third_stride);
+    visit_engine_goal(*cfg, [&](auto e) {
+      using E = decltype(e);
+      if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
+        hipLaunchKernelGGL((wv::lidar_graph_wave_kernel<E::ENGINE, E::GOAL, E::SD, 3>), wave_step_grid(st.n_env), dim3(256),
+                           kWaveStepLds<E::SD>, s, *cfg, st, io->goal, io->goal_stride);
+    });
     return (int)hipGetLastError();
   }
   const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k, !mpe);

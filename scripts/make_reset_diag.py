@@ -23,8 +23,7 @@ marks = [("  if (tid == 0) rng_count = (uint32_t)n_ob_draws;\n  __syncthreads();
          ("        for (int c = 0; c < SD; ++c) third[o * SD + c] = c == 0 ? cx : (c == 1 ? cy : 0.0f);\n"
           "      }\n    }\n  }\n  __syncthreads();\n", 4),
          ("  if (states_only) {  // the wave step kernel builds the graph from these rows (dgppo_env_reset)\n", 5),
-         ("    write_graph<ENGINE, GOAL, SD>(cfg, d, nxt, goal, mpe ? third : lds + cv.hits, out, vec4, tid, BLOCK);\n"
-          "  }\n", 7)]
+         ("  graph_of_staged_rows<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);\n", 7)]  # (ray cast + graph)
 pos = b0
 for anchor, k in marks:
     i = src.index(anchor, pos) + len(anchor)
