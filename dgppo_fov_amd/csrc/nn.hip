@@ -347,15 +347,19 @@ __global__ __launch_bounds__(256) void agent_mean_bwd_kernel(const float* dy, fl
 }
 
 // ---- TanhNormal head (distribution.py:10-66 + tfp Normal / Tanh / Independent) ----------------
+// asymptotic series for the far left tail (z <= -10): Phi(z) = phi(z) s(z) / (-z)
+__device__ __forceinline__ float ndtr_tail_s(float z) {
+  const float z2 = z * z;
+  return 1.0f - 1.0f / z2 + 3.0f / (z2 * z2) - 15.0f / (z2 * z2 * z2);
+}
 __device__ __forceinline__ float log_ndtr_f(float z) {
   if (z > -10.0f) return logf(0.5f * erfcf(-z * 0.70710678118654752f));
-  // asymptotic series for the far left tail
-  const float z2 = z * z;
-  const float s = 1.0f - 1.0f / z2 + 3.0f / (z2 * z2) - 15.0f / (z2 * z2 * z2);
-  return -0.5f * z2 - logf(-z) - 0.91893853320467274f + logf(s);
+  return -0.5f * z * z - logf(-z) - 0.91893853320467274f + logf(ndtr_tail_s(z));
 }
-// d/dz log Phi(z) = phi(z) / Phi(z)
+// d/dz log Phi(z) = phi(z) / Phi(z); in the tail -z / s, not exp(log phi - log Phi): both logs are about -z^2 / 2 and
+// their difference loses every digit by z = -1e4
 __device__ __forceinline__ float dlog_ndtr_f(float z) {
+  if (z <= -10.0f) return -z / ndtr_tail_s(z);
   const float lp = -0.5f * z * z - 0.91893853320467274f;
   return expf(lp - log_ndtr_f(z));
 }
@@ -857,7 +861,8 @@ extern "C" int64_t dgppo_layernorm_bwd_workspace_floats(int64_t rows, int32_t F)
 extern "C" int dgppo_layernorm_bwd(const float* x, const float* y, const float* dy, const float* scale,
                                    const float* mean, const float* rstd, float* dx, float* dscale, float* dbias,
                                    int64_t rows, int32_t F, int32_t relu, float* workspace, void* stream) {
-  if (rows < 0 || F < 1 || !x || !dy || !scale || !dx || !dscale || !dbias || !workspace || (relu && !y))
+  if (rows < 0 || F < 1 || !x || !dy || !scale || !mean || !rstd || !dx || !dscale || !dbias || !workspace ||
+      (relu && !y))
     return DGPPO_EINVAL;
   if (rows == 0) return 0;
   const RowSplit sp = row_split(rows, 64);

@@ -492,6 +492,8 @@ def gather_env_steps(src: List[Tensor], dst: List[Tensor], envs: Tensor) -> None
             inner *= a.shape[d]
         f.src, f.dst, f.row_elems = _p(a), _p(b), inner
         f.src_tstride, f.src_estride = a.stride(1), a.stride(0)
+    if envs.shape[0] == 0:  # an empty selection gathers nothing (an empty tensor has no address to pass)
+        return
     _lib.check(_lib.load().dgppo_gather_env_steps(fields, len(src), _p(envs), int(envs.shape[0]), T, _stream(envs)),
                "dgppo_gather_env_steps")
 
