@@ -193,6 +193,12 @@ class GemmArgs(ctypes.Structure):
     ]
 
 
+class GemmPlan(ctypes.Structure):  # dgppo_gemm_plan_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("path", "form", "ntw", "ncg", "nch", "vec", "extra", "epi", "mt", "nt",
+                                               "unroll", "flat", "pipe", "chunks", "split_k", "grid")] + \
+               [("units", ctypes.c_int64), ("lds_bytes", ctypes.c_int64)]
+
+
 class GruSeqArgs(ctypes.Structure):
     _fields_ = [
         ("Q", ctypes.c_int32), ("L", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("H", ctypes.c_int32),
@@ -325,6 +331,7 @@ SIGNATURES = {
     "dgppo_gemm_wgrad_grouped_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs), ctypes.c_int]),
     "dgppo_gemm_wgrad_grouped": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_int, c_f32p, ctypes.c_void_p]),
     "dgppo_gemm": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_void_p]),
+    "dgppo_gemm_plan": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.POINTER(GemmPlan)]),
     "dgppo_gnn_attn_fwd": (ctypes.c_int, [ctypes.POINTER(GnnAttnArgs), ctypes.c_void_p]),
     "dgppo_gnn_attn_bwd": (ctypes.c_int, [ctypes.POINTER(GnnAttnArgs), ctypes.c_void_p]),
     "dgppo_relu_bwd": (ctypes.c_int, [_V, _V, _I64, _V]),

@@ -1145,21 +1145,62 @@ void wgrad_shape(int M, int N, int* MT, int* NT) {
   if (*MT == 3 && *NT == 6) *MT = 2;
 }
 
+// a grouping whose group stride is grp rows is the plain row layout: drop it (the flat kernel's addressing)
+void wgrad_normalise(dgppo_gemm_args* q) {
+  if (q->a_grp > 0 && q->a_gstride == (int64_t)q->a_grp * q->lda) q->a_grp = 0;
+  if (q->b_grp > 0 && q->b_gstride == (int64_t)q->b_grp * q->ldb) q->b_grp = 0;
+}
+
+// every (MT, NT) tile-group shape the weight-gradient kernel is instantiated for: the one list the plan and the
+// launch both expand
+#define DG_WGRAD_SHAPES(X)                                                                                   \
+  X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 6) X(2, 1) X(2, 2) X(2, 3) X(2, 6) X(3, 1) X(3, 2) X(3, 3) X(4, 1) X(4, 2) \
+  X(4, 3)
+
+// the wgrad fields of the plan: tile-group shape, row chunks, loop form, grid and dynamic LDS
+int plan_wgrad(const dgppo_gemm_args* p0, dgppo_gemm_plan_info* o) {
+  dgppo_gemm_args q = *p0;
+  wgrad_normalise(&q);
+  int MT, NT;
+  wgrad_shape(q.M, q.N, &MT, &NT);
+  o->mt = MT;
+  o->nt = NT;
+  o->chunks = wgrad_chunk_count(q.K);
+  o->flat = q.a_grp <= 0 && q.b_grp <= 0;
+  o->pipe = wgrad_pipe() != 0;
+  if (wgrad_unroll() == 8 && MT * NT <= 4 && o->flat && o->pipe) o->unroll = 8;
+  else if (wgrad_unroll() >= 4 && MT * NT <= 4) o->unroll = 4;
+  else o->unroll = 2;
+  const int gm = (q.M + MT * 32 - 1) / (MT * 32), gn = (q.N + NT * 32 - 1) / (NT * 32);
+  o->ncg = gn;
+  o->grid = o->chunks * gm * gn;
+  o->units = o->grid;
+  o->lds_bytes = (int64_t)(((size_t)4 * MT * 32 * (NT * 32 + 1) + 2 * dgppo::kWWaves * NT * 32) * sizeof(float));
+  if (o->chunks > 1 && !p0->workspace) return DGPPO_EINVAL;
+  // (4, 3) and (2, 6), which only DGPPO_WGRAD_MAXACC > 8 selects, need more than the 160 KB of LDS a workgroup can
+  // have: refused here instead of failing at the launch
+  if (o->lds_bytes > 160 * 1024) return DGPPO_EINVAL;
+#define DG_W(a, b) \
+  if (MT == a && NT == b) return 0;
+  DG_WGRAD_SHAPES(DG_W)
+#undef DG_W
+  return DGPPO_EINVAL;
+}
+
 template <int MT, int NT>
-void launch_wgrad_t(const dgppo_gemm_args* p, int chunks, hipStream_t s) {
-  const int gm = (p->M + MT * 32 - 1) / (MT * 32), gn = (p->N + NT * 32 - 1) / (NT * 32);
-  const size_t lds = ((size_t)4 * MT * 32 * (NT * 32 + 1) + 2 * dgppo::kWWaves * NT * 32) * sizeof(float);
-  const dim3 grid(chunks * gm * gn, 1, p->batch);
-  const bool flat = p->a_grp <= 0 && p->b_grp <= 0;
+void launch_wgrad_t(const dgppo_gemm_args* p, const dgppo_gemm_plan_info& pl, hipStream_t s) {
+  const int chunks = pl.chunks, gn = pl.ncg;
+  const size_t lds = (size_t)pl.lds_bytes;
+  const dim3 grid(pl.grid, 1, p->batch);
+  const bool flat = pl.flat, pipe = pl.pipe;
 #define DG_WL(U, FL, PP)                                                                                       \
   do {                                                                                                         \
     if (lds > 64 * 1024) dgppo::allow_lds((const void*)dgppo::gemm_wgrad_kernel<MT, NT, U, FL, PP>);         \
     hipLaunchKernelGGL((dgppo::gemm_wgrad_kernel<MT, NT, U, FL, PP>), grid, dim3(512), lds, s, *p, chunks, gn); \
   } while (0)
-  const bool pipe = wgrad_pipe();
-  if (wgrad_unroll() == 8 && MT * NT <= 4 && flat && pipe) {
+  if (pl.unroll == 8) {
     DG_WL(8, true, true);
-  } else if (wgrad_unroll() >= 4 && MT * NT <= 4) {
+  } else if (pl.unroll == 4) {
     if (pipe) {
       if (flat) DG_WL(4, true, true);
       else DG_WL(4, false, true);
@@ -1179,20 +1220,14 @@ void launch_wgrad_t(const dgppo_gemm_args* p, int chunks, hipStream_t s) {
 #undef DG_WL
 }
 
-int launch_wgrad(const dgppo_gemm_args* p0, hipStream_t s) {
-  // a grouping whose group stride is grp rows is the plain row layout: drop it (the flat kernel's addressing)
+int launch_wgrad(const dgppo_gemm_args* p0, const dgppo_gemm_plan_info& pl, hipStream_t s) {
   dgppo_gemm_args q = *p0;
-  if (q.a_grp > 0 && q.a_gstride == (int64_t)q.a_grp * q.lda) q.a_grp = 0;
-  if (q.b_grp > 0 && q.b_gstride == (int64_t)q.b_grp * q.ldb) q.b_grp = 0;
+  wgrad_normalise(&q);
   const dgppo_gemm_args* p = &q;
-  int MT, NT;
-  wgrad_shape(p->M, p->N, &MT, &NT);
-  const int chunks = wgrad_chunk_count(p->K);
-  if (chunks > 1 && !p->workspace) return DGPPO_EINVAL;
+  const int MT = pl.mt, NT = pl.nt, chunks = pl.chunks;
 #define DG_W(a, b) \
-  if (MT == a && NT == b) { launch_wgrad_t<a, b>(p, chunks, s); goto launched; }
-  DG_W(1, 1) DG_W(1, 2) DG_W(1, 3) DG_W(1, 4) DG_W(1, 6) DG_W(2, 1) DG_W(2, 2) DG_W(2, 3) DG_W(2, 6)
-  DG_W(3, 1) DG_W(3, 2) DG_W(3, 3) DG_W(4, 1) DG_W(4, 2) DG_W(4, 3)
+  if (MT == a && NT == b) { launch_wgrad_t<a, b>(p, pl, s); goto launched; }
+  DG_WGRAD_SHAPES(DG_W)
 #undef DG_W
   return DGPPO_EINVAL;
 launched:
@@ -1214,42 +1249,42 @@ void rows_split(int N, int* ntw, int* ncg) {
   else { *ntw = 2; *ncg = (nt + 1) / 2; }
 }
 
-// kernel choice, grid and dynamic LDS of a rows-path call (shared by the launch and dgppo_gemm_partial_rows)
-struct RowsPlan {
-  int ntw, ncg, K16, grid;
-  size_t lds;
-  bool vec, use_pf, use_breg;
-};
-RowsPlan rows_plan(const dgppo_gemm_args* p) {
-  RowsPlan r;
-  rows_split(p->N, &r.ntw, &r.ncg);
-  r.K16 = (p->K + 15) & ~15;
-  r.lds = (size_t)r.K16 * (32 * r.ntw * r.ncg + 1) * sizeof(float);
-  const int64_t units = (int64_t)((p->M + 31) / 32) * r.ncg;
-  int per_cu = (int)((160 * 1024) / (r.lds > 0 ? r.lds : 1));
+// kernel choice, grid and dynamic LDS of a rows-path call: the rows fields of the plan (shared by the launch,
+// dgppo_gemm_plan and dgppo_gemm_partial_rows)
+void rows_decide(const dgppo_gemm_args* p, dgppo_gemm_plan_info* o) {
+  rows_split(p->N, &o->ntw, &o->ncg);
+  const int K16 = (p->K + 15) & ~15;
+  o->nch = K16 / 16;
+  const size_t lds = (size_t)K16 * (32 * o->ntw * o->ncg + 1) * sizeof(float);
+  o->lds_bytes = (int64_t)lds;
+  o->units = (int64_t)((p->M + 31) / 32) * o->ncg;
+  int per_cu = (int)((160 * 1024) / (lds > 0 ? lds : 1));
   per_cu = per_cu < 1 ? 1 : per_cu > 5 ? 5 : per_cu;
   static int knob = -2;
   if (knob == -2) {
     const char* v = getenv("DGPPO_ROWS_WG_PER_CU");
     knob = v ? atoi(v) : -1;
   }
-  r.vec = (p->K % 8 == 0) && (p->lda % 4 == 0) && (((uintptr_t)p->A & 15) == 0) &&
-          (p->a_grp <= 0 || p->a_gstride % 4 == 0) && (p->stride_a % 4 == 0);
+  const bool vec = (p->K % 8 == 0) && (p->lda % 4 == 0) && (((uintptr_t)p->A & 15) == 0) &&
+                   (p->a_grp <= 0 || p->a_gstride % 4 == 0) && (p->stride_a % 4 == 0);
+  o->vec = vec;
   // kernel choice and workgroups per CU, measured on the update's shapes (scripts/ab_gemm_pf.sh,
   // profiles/r03_gemm_rows_ab.txt, 131072 rows): the whole-unit prefetch form wins for K <= 32 and for N > 64
   // (N99 K32 35.7 -> 27.8 us, N64 K32 + addend 39.8 -> 22.4, N192 K32 52.4 -> 41.3, N192 K64 68.8 -> 63.9) at 3
   // workgroups per CU; the B-in-registers form stays best for N <= 64, K = 64 at 2 (28.0 -> 24.4-24.8 us)
   static const int pf = env_knob("DGPPO_ROWS_PF", 1);
   static const int breg = env_knob("DGPPO_ROWS_BREG", 1);
-  r.use_pf = r.vec && pf && r.K16 <= 64 && (r.K16 <= 32 || r.ncg > 1 || !breg);
-  r.use_breg = !r.use_pf && r.vec && breg && r.ncg == 1 && r.K16 <= 64;
-  if (r.use_pf && per_cu > 3) per_cu = 3;
-  if (r.use_breg && per_cu > 2) per_cu = 2;
+  const bool use_pf = vec && pf && K16 <= 64 && (K16 <= 32 || o->ncg > 1 || !breg);
+  const bool use_breg = !use_pf && vec && breg && o->ncg == 1 && K16 <= 64;
+  o->form = use_pf ? DGPPO_GEMM_ROWS_PREFETCH : use_breg ? DGPPO_GEMM_ROWS_BREG : DGPPO_GEMM_ROWS_PLAIN;
+  if (use_pf && per_cu > 3) per_cu = 3;
+  if (use_breg && per_cu > 2) per_cu = 2;
   if (knob > 0 && knob < per_cu) per_cu = knob;
-  const int64_t want = (units + 3) / 4, cap = 256LL * per_cu;
-  r.grid = (int)(want < cap ? want : cap);
-  if (r.grid < 1) r.grid = 1;
-  return r;
+  const int64_t want = (o->units + 3) / 4, cap = 256LL * per_cu;
+  o->grid = (int)(want < cap ? want : cap);
+  if (o->grid < 1) o->grid = 1;
+  o->extra = (p->addend != nullptr ? 1 : 0) | (p->beta != 0.0f ? 2 : 0);
+  o->epi = p->epi;
 }
 
 // EPI != 0 instantiates only the combinations the epilogue supports (LayerNorm: NTW 2, no beta C / addend;
@@ -1259,16 +1294,42 @@ constexpr bool epi_combo() {
   return EPI == 0 || (EPI == dgppo::kEpiMask && (EXTRA == 0 || EXTRA == 2)) || (NTW == 2 && EXTRA == 0);
 }
 
+// the rows fields of the plan, and whether the call's epilogue and shape have a kernel
+int plan_rows(const dgppo_gemm_args* p, dgppo_gemm_plan_info* o) {
+  rows_decide(p, o);
+  switch (p->epi) {
+    case 0:
+      if (o->ntw != 1 && o->ntw != 2 && o->ntw != 3 && o->ntw != 6) return DGPPO_EINVAL;
+      break;
+    case dgppo::kEpiMask:
+      if (!p->mask || p->addend || p->relu) return DGPPO_EINVAL;
+      if (o->ntw != 1 && o->ntw != 2) return DGPPO_EINVAL;
+      break;
+    case dgppo::kEpiLnFwd:
+    case dgppo::kEpiLnBwd:
+      if (p->N != 64 || o->ntw != 2 || o->ncg != 1 || p->batch != 1 || p->addend || p->beta != 0.0f || p->relu ||
+          !p->ln_scale || !p->ln_bias || !p->ln_h || !p->ln_mean || !p->ln_rstd ||
+          (p->epi == dgppo::kEpiLnBwd && !p->ln_part))
+        return DGPPO_EINVAL;
+      break;
+    default:
+      return DGPPO_EINVAL;
+  }
+  // the prefetch and B-in-registers forms exist for 1..4 k-chunks
+  if (o->form != DGPPO_GEMM_ROWS_PLAIN && (o->nch < 1 || o->nch > 4)) return DGPPO_EINVAL;
+  return 0;
+}
+
 template <int NTW, int EPI>
-int launch_rows_t(const dgppo_gemm_args* p, const RowsPlan& r, hipStream_t s) {
-  const int extra = (p->addend != nullptr ? 1 : 0) | (p->beta != 0.0f ? 2 : 0);
-  const int ncg = r.ncg, grid = r.grid, K16 = r.K16;
-  const size_t lds = r.lds;
+int launch_rows_t(const dgppo_gemm_args* p, const dgppo_gemm_plan_info& r, hipStream_t s) {
+  const int extra = r.extra, ncg = r.ncg, grid = r.grid, nch = r.nch;
+  const size_t lds = (size_t)r.lds_bytes;
+  const bool vec = r.vec != 0;
   bool done = false;
-  if (r.use_pf) {
+  if (r.form == DGPPO_GEMM_ROWS_PREFETCH) {
 #define DG_PF(c, x)                                                                                               \
   if constexpr (epi_combo<EPI, NTW, x>())                                                                         \
-    if (!done && K16 == 16 * c && extra == x) {                                                                   \
+    if (!done && nch == c && extra == x) {                                                                        \
       hipLaunchKernelGGL((dgppo::gemm_rows_pf_kernel<NTW, c, x, EPI>), dim3(grid, 1, p->batch), dim3(256), lds, s, \
                          *p, ncg);                                                                               \
       done = true;                                                                                                \
@@ -1276,10 +1337,10 @@ int launch_rows_t(const dgppo_gemm_args* p, const RowsPlan& r, hipStream_t s) {
     DG_PF(1, 0) DG_PF(1, 1) DG_PF(1, 2) DG_PF(1, 3) DG_PF(2, 0) DG_PF(2, 1) DG_PF(2, 2) DG_PF(2, 3)
     DG_PF(3, 0) DG_PF(3, 1) DG_PF(3, 2) DG_PF(3, 3) DG_PF(4, 0) DG_PF(4, 1) DG_PF(4, 2) DG_PF(4, 3)
 #undef DG_PF
-  } else if (r.use_breg) {
+  } else if (r.form == DGPPO_GEMM_ROWS_BREG) {
 #define DG_RB(c, x)                                                                                                  \
   if constexpr (epi_combo<EPI, NTW, x>())                                                                            \
-    if (!done && K16 == 16 * c && extra == x) {                                                                      \
+    if (!done && nch == c && extra == x) {                                                                           \
       hipLaunchKernelGGL((dgppo::gemm_rows_breg_kernel<NTW, c, x, EPI>), dim3(grid, 1, p->batch), dim3(256), lds, s, \
                          *p);                                                                                        \
       done = true;                                                                                                   \
@@ -1290,7 +1351,7 @@ int launch_rows_t(const dgppo_gemm_args* p, const RowsPlan& r, hipStream_t s) {
   } else {
 #define DG_R(v, x)                                                                                                  \
   if constexpr (epi_combo<EPI, NTW, x>())                                                                           \
-    if (!done && r.vec == v && extra == x) {                                                                        \
+    if (!done && vec == v && extra == x) {                                                                          \
       hipLaunchKernelGGL((dgppo::gemm_rows_kernel<NTW, v, x, EPI>), dim3(grid, 1, p->batch), dim3(256), lds, s, *p, \
                          ncg);                                                                                      \
       done = true;                                                                                                  \
@@ -1302,9 +1363,8 @@ int launch_rows_t(const dgppo_gemm_args* p, const RowsPlan& r, hipStream_t s) {
   return done ? 0 : DGPPO_EINVAL;
 }
 
-int launch_rows(const dgppo_gemm_args* p, hipStream_t s) {
-  const RowsPlan r = rows_plan(p);
-  switch (p->epi) {
+int launch_rows(const dgppo_gemm_args* p, const dgppo_gemm_plan_info& r, hipStream_t s) {
+  switch (r.epi) {
     case 0:
       switch (r.ntw) {
         case 1: return launch_rows_t<1, 0>(p, r, s);
@@ -1314,25 +1374,58 @@ int launch_rows(const dgppo_gemm_args* p, hipStream_t s) {
       }
       return DGPPO_EINVAL;
     case dgppo::kEpiMask:
-      if (!p->mask || p->addend || p->relu) return DGPPO_EINVAL;
       if (r.ntw == 1) return launch_rows_t<1, dgppo::kEpiMask>(p, r, s);
       if (r.ntw == 2) return launch_rows_t<2, dgppo::kEpiMask>(p, r, s);
       return DGPPO_EINVAL;
-    case dgppo::kEpiLnFwd:
-    case dgppo::kEpiLnBwd:
-      if (p->N != 64 || r.ntw != 2 || r.ncg != 1 || p->batch != 1 || p->addend || p->beta != 0.0f || p->relu ||
-          !p->ln_scale || !p->ln_bias || !p->ln_h || !p->ln_mean || !p->ln_rstd ||
-          (p->epi == dgppo::kEpiLnBwd && !p->ln_part))
-        return DGPPO_EINVAL;
-      return p->epi == dgppo::kEpiLnFwd ? launch_rows_t<2, dgppo::kEpiLnFwd>(p, r, s) : launch_rows_t<2, dgppo::kEpiLnBwd>(p, r, s);
+    case dgppo::kEpiLnFwd: return launch_rows_t<2, dgppo::kEpiLnFwd>(p, r, s);
+    case dgppo::kEpiLnBwd: return launch_rows_t<2, dgppo::kEpiLnBwd>(p, r, s);
   }
   return DGPPO_EINVAL;
 }
+
+// every host decision of dgppo_gemm: the argument checks, the path and the kernel of that path
+int gemm_plan(const dgppo_gemm_args* p, dgppo_gemm_plan_info* o) {
+  *o = dgppo_gemm_plan_info{};
+  o->path = DGPPO_GEMM_PATH_NONE;
+  if (!p || p->M < 0 || p->N < 0 || p->K < 0 || p->batch < 1 || p->split_k < 1 || p->split_k > 4096)
+    return DGPPO_EINVAL;
+  if (p->M == 0 || p->N == 0) return 0;
+  if (!p->A || !p->B || !p->C) return DGPPO_EINVAL;
+  const GemmPath path = gemm_path(p);
+  if (p->bias_grad && path != kPathWgrad) return DGPPO_EINVAL;
+  if (p->epi && path != kPathRows) return DGPPO_EINVAL;
+  int rc = 0;
+  if (path == kPathWgrad) {
+    rc = plan_wgrad(p, o);
+    o->path = DGPPO_GEMM_PATH_WGRAD;
+  } else if (path == kPathRows) {
+    rc = plan_rows(p, o);
+    o->path = DGPPO_GEMM_PATH_ROWS;
+  } else {
+    o->path = DGPPO_GEMM_PATH_TILE;
+    o->split_k = p->split_k;
+    o->units = (int64_t)((p->M + dgppo::kBM - 1) / dgppo::kBM) * ((p->N + dgppo::kBN - 1) / dgppo::kBN);
+    o->grid = (int)o->units;
+    if (p->split_k > 1 && !p->workspace) rc = DGPPO_EINVAL;
+  }
+  if (rc) {
+    *o = dgppo_gemm_plan_info{};
+    o->path = DGPPO_GEMM_PATH_NONE;
+  }
+  return rc;
+}
 }  // namespace
+
+extern "C" int dgppo_gemm_plan(const dgppo_gemm_args* p, dgppo_gemm_plan_info* out) {
+  if (!out) return DGPPO_EINVAL;
+  return gemm_plan(p, out);
+}
 
 extern "C" int64_t dgppo_gemm_partial_rows(const dgppo_gemm_args* p) {
   if (!p || p->M < 1 || p->N < 1 || gemm_path(p) != kPathRows) return 0;
-  return rows_plan(p).grid;
+  dgppo_gemm_plan_info pl{};
+  rows_decide(p, &pl);  // the grid alone: the call's ln_part is sized from this before it exists
+  return pl.grid;
 }
 
 extern "C" int64_t dgppo_gemm_workspace_floats(const dgppo_gemm_args* p) {
@@ -1351,25 +1444,19 @@ extern "C" int64_t dgppo_gemm_workspace_floats(const dgppo_gemm_args* p) {
 }
 
 extern "C" int dgppo_gemm(const dgppo_gemm_args* p, void* stream) {
-  if (!p || p->M < 0 || p->N < 0 || p->K < 0 || p->batch < 1 || p->split_k < 1 || p->split_k > 4096)
-    return DGPPO_EINVAL;
-  if (p->M == 0 || p->N == 0) return 0;
-  if (!p->A || !p->B || !p->C) return DGPPO_EINVAL;
-  if (p->bias_grad && gemm_path(p) != kPathWgrad) return DGPPO_EINVAL;
-  if (p->epi && gemm_path(p) != kPathRows) return DGPPO_EINVAL;
+  dgppo_gemm_plan_info pl;
+  if (const int rc = gemm_plan(p, &pl)) return rc;
+  if (pl.path == DGPPO_GEMM_PATH_NONE) return 0;
   hipStream_t s = (hipStream_t)stream;
-  const GemmPath path = gemm_path(p);
-  if (path == kPathWgrad) {
-    if (launch_wgrad(p, s)) return DGPPO_EINVAL;
+  if (pl.path == DGPPO_GEMM_PATH_WGRAD) {
+    if (launch_wgrad(p, pl, s)) return DGPPO_EINVAL;
     return (int)hipGetLastError();
   }
-  if (path == kPathRows) {
-    if (launch_rows(p, s)) return DGPPO_EINVAL;
+  if (pl.path == DGPPO_GEMM_PATH_ROWS) {
+    if (launch_rows(p, pl, s)) return DGPPO_EINVAL;
     return (int)hipGetLastError();
   }
-  if (p->split_k > 1 && !p->workspace) return DGPPO_EINVAL;
-  const int tiles = ((p->M + dgppo::kBM - 1) / dgppo::kBM) * ((p->N + dgppo::kBN - 1) / dgppo::kBN);
-  hipLaunchKernelGGL(dgppo::gemm_kernel, dim3(tiles, p->split_k, p->batch), dim3(256), 0, s, *p);
+  hipLaunchKernelGGL(dgppo::gemm_kernel, dim3(pl.grid, p->split_k, p->batch), dim3(256), 0, s, *p);
   if (p->split_k > 1) {
     const int64_t total = (int64_t)p->M * p->N * p->batch;
     const int64_t nb = (total + 255) / 256;

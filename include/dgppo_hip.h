@@ -288,7 +288,8 @@ typedef struct dgppo_gemm_args {
                         (the dense layer's db fused into its dW = X^T dY), or NULL */
   /* ABI 9: elementwise pass fused into the epilogue of the row-GEMM paths (!trans_a, N <= 192, K <= 256; else
    * DGPPO_EINVAL).  epi 0: none.  1: relu mask, C = mask > 0 ? result : 0 (mask rows addressed like C with
-   * ld_mask; the ReLU backward of the layer that produced `mask`, nn/gnn.py:116).  2: LayerNorm(64) + ReLU
+   * ld_mask; the ReLU backward of the layer that produced `mask`, nn/gnn.py:116; the mask has no batch stride:
+   * with batch > 1 every batch entry is gated by the same (M, N) mask).  2: LayerNorm(64) + ReLU
    * forward (flax LayerNorm eps 1e-6 + relu, nn/mlp.py:20-30; N == 64, no beta / addend / relu): ln_h (M, 64)
    * <- result, C <- relu(((ln_h - mean) rstd) ln_scale + ln_bias), ln_mean / ln_rstd (M) <- the row
    * statistics.  3: its backward: the result is dy; with ln_h, ln_mean and ln_rstd as epi 2 wrote them (the
@@ -313,6 +314,31 @@ int dgppo_gemm_wgrad_grouped(const dgppo_gemm_args* args, int n, float* workspac
 /* rows of ln_part an epi 3 call writes (its workgroup count; 0 when the call is not on the row-GEMM paths) */
 int64_t dgppo_gemm_partial_rows(const dgppo_gemm_args* args);
 int dgppo_gemm(const dgppo_gemm_args* args, void* stream);
+/* The host decisions of a dgppo_gemm call, without launching anything (needs no GPU): dgppo_gemm itself launches
+ * from this struct.  Returns DGPPO_EINVAL exactly where dgppo_gemm(args) would (then path is NONE), else 0.
+ * The fields name the kernel template instantiation that runs (the DGPPO_ROWS_* / DGPPO_WGRAD_* environment knobs
+ * are read once per process).  Fields of another path are 0. */
+#define DGPPO_GEMM_PATH_NONE (-1) /* M == 0 or N == 0: nothing is launched */
+#define DGPPO_GEMM_PATH_TILE 0
+#define DGPPO_GEMM_PATH_ROWS 1
+#define DGPPO_GEMM_PATH_WGRAD 2
+#define DGPPO_GEMM_ROWS_PLAIN 0    /* chunk-at-a-time A pipeline, B read from LDS */
+#define DGPPO_GEMM_ROWS_PREFETCH 1 /* whole-unit prefetch */
+#define DGPPO_GEMM_ROWS_BREG 2     /* B in registers */
+typedef struct dgppo_gemm_plan_info {
+  int32_t path;                  /* DGPPO_GEMM_PATH_* */
+  int32_t form;                  /* rows: DGPPO_GEMM_ROWS_* */
+  int32_t ntw, ncg;              /* rows: 32-column tiles per wave unit, column groups; wgrad: ncg = tile groups along N */
+  int32_t nch;                   /* rows: 16-wide k-chunks (a template parameter of the prefetch / B-in-registers forms) */
+  int32_t vec, extra, epi;       /* rows: 16-byte A loads; bit 0 addend, bit 1 beta C; args.epi */
+  int32_t mt, nt, unroll, flat, pipe, chunks; /* wgrad: tile-group shape, row pairs in flight, ungrouped rows,
+                                                 two-stage loop, row chunks (> 1: a reduce launch follows) */
+  int32_t split_k;               /* tile */
+  int32_t grid;                  /* workgroups along x (times batch along z; tile: times split_k along y) */
+  int64_t units;                 /* rows: wave work units (32-row panels x ncg); tile / wgrad: = grid */
+  int64_t lds_bytes;             /* dynamic LDS of the launch */
+} dgppo_gemm_plan_info;
+int dgppo_gemm_plan(const dgppo_gemm_args* args, dgppo_gemm_plan_info* out);
 
 /* GraphTransformer attention core (dgppo/nn/gnn.py:78-117 + jraph.segment_softmax/segment_sum),
  * per RECEIVING AGENT: only agents receive messages in the DGPPO env graphs, so with

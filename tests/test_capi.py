@@ -53,6 +53,7 @@ def _c_layout(struct, fields):
 @pytest.mark.parametrize("pystruct,cname", [(_lib.EnvCfg, "dgppo_env_cfg"), (_lib.EnvStepIO, "dgppo_env_step_io"),
                                             (_lib.EnvResetIO, "dgppo_env_reset_io"),
                                             (_lib.GemmArgs, "dgppo_gemm_args"),
+                                            (_lib.GemmPlan, "dgppo_gemm_plan_info"),
                                             (_lib.GnnAttnArgs, "dgppo_gnn_attn_args"),
                                             (_lib.GnnLayerArgs, "dgppo_gnn_layer_args"),
                                             (_lib.GnnValueTail, "dgppo_gnn_value_tail"),
