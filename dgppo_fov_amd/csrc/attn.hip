@@ -26,7 +26,7 @@
 #include <string.h>
 
 #include "../../include/dgppo_hip.h"
-#include "lanes.h"
+#include "attn_core.h"
 
 namespace dgppo {
 
@@ -45,8 +45,6 @@ __device__ __forceinline__ float q_dot_bk(const dgppo_gnn_attn_args& p, int64_t 
 }
 namespace {
 
-constexpr int kH = 3;         // heads (GraphTransformer num_heads of the reference GNN)
-constexpr int kD0 = 8;        // max raw feature width in agent mode
 constexpr int kMaxBlocks = 2048;
 
 template <int CP>
@@ -1014,7 +1012,7 @@ int pick_cp(int C) {
 // sub-round; the softmax reductions are DPP lane shuffles; the weighted sums read float4 rows.
 // ================================================================================================
 namespace fwd2 {
-constexpr int kRows = 16, kSR = 2, kQP = 100;
+constexpr int kSR = 2, kQP = 100;
 // xs row pitch: x (DM floats; the pre-transform writes 32) then the edge features at column EC
 template <int DM>
 struct Pitch {
@@ -1037,8 +1035,7 @@ constexpr size_t lds_floats() {
 template <int DM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void attn_fwd2r_kernel(
     dgppo_gnn_attn_args p) {
-  using lanes::f32x4;
-  constexpr int kRows = fwd2::kRows, kSR = fwd2::kSR, kQP = fwd2::kQP;
+  constexpr int kSR = fwd2::kSR, kQP = fwd2::kQP;
   static_assert(DM == 8 || DM == 16 || DM == 32, "fwd2r instantiations");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* qts = lds;                 // [16][100]: qt_h (32-float stride per head) | beta_h at 96 + h
@@ -1112,46 +1109,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
       float xr[kD0];
 #pragma unroll
       for (int k = 0; k < kD0; ++k) xr[k] = x[k];
-#pragma unroll
-      for (int q = 0; q < DM / 4; ++q) {
-        const f32x4 b = *(const f32x4*)(preb + 4 * q);
-        x[4 * q] = b[0];
-        x[4 * q + 1] = b[1];
-        x[4 * q + 2] = b[2];
-        x[4 * q + 3] = b[3];
-      }
-#pragma unroll
-      for (int k = 0; k < kD0; ++k)
-#pragma unroll
-        for (int q = 0; q < DM / 4; ++q) {
-          const f32x4 w = *(const f32x4*)(preW + k * 32 + 4 * q);
-          x[4 * q] += xr[k] * w[0];
-          x[4 * q + 1] += xr[k] * w[1];
-          x[4 * q + 2] += xr[k] * w[2];
-          x[4 * q + 3] += xr[k] * w[3];
-        }
-#pragma unroll
-      for (int d = 0; d < DM; ++d) x[d] = x[d] > 0.0f ? x[d] : 0.0f;
+      pre_row<kD0>(xr, preW, preb, x);
     }
     // logits, softmax over the row's candidates, attention weights out
     const float* qt = qts + rl * kQP;
     float aw[kH];
-#pragma unroll
-    for (int h = 0; h < kH; ++h) {
-      float acc = 0.0f;
-#pragma unroll
-      for (int q = 0; q < DM / 4; ++q)
-        if (q < TQ) {
-          const f32x4 qq = ((const f32x4*)(qt + 32 * h))[q];
-          acc += x[4 * q] * qq[0] + x[4 * q + 1] * qq[1] + x[4 * q + 2] * qq[2] + x[4 * q + 3] * qq[3];
-        }
-      const float lg = ok ? (acc + qt[96 + h]) * p.scale : -INFINITY;
-      const float mx = lanes::max32(lg);
-      const float ex = ok ? expf(lg - mx) : 0.0f;
-      const float sm = lanes::sum32(ex);
-      aw[h] = ok ? ex / sm : 0.0f;
-      if (active && c < C && p.attn) p.attn[((int64_t)row * H + h) * C + c] = aw[h];
-    }
+    // (the sinks capture locals only, not the kernel argument struct: see gnn_layer.hip stage 4)
+    float* const attn = p.attn;
+    head_weights(x, qt, 32, TQ, p.scale, ok, aw, [=](int h, float w) {
+      if (active && c < C && attn) attn[((int64_t)row * H + h) * C + c] = w;
+    });
     float* o = p.xcat + (int64_t)row * W;
     // xbar_h = sum_c a_h x_c
 #pragma unroll
@@ -1159,13 +1126,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
       float v[DM];
 #pragma unroll
       for (int d = 0; d < DM; ++d) v[d] = aw[h] * x[d];
-      int cnt;
-      const int base = lanes::treduce32(v, cnt);
-#pragma unroll
-      for (int j = 0; j < lanes::tr_final<DM>(); ++j) {
-        const int q = base + j;
-        if (active && j < cnt && q < D) o[h * D + q] = v[j];
-      }
+      wsum(v, [=](int q, float t) { if (q < D) o[h * D + q] = t; }, active);
     }
     // [ebar_h (4) | sig_h] of the three heads
     {
@@ -1176,14 +1137,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         for (int j = 0; j < 4; ++j) v[h * 5 + j] = aw[h] * ef[j];
         v[h * 5 + 4] = aw[h];
       }
-      int cnt;
-      const int base = lanes::treduce32(v, cnt);
-#pragma unroll
-      for (int j = 0; j < lanes::tr_final<NEV>(); ++j) {
-        const int q = base + j;
+      wsum(v, [=](int q, float t) {
         const int h = q / 5, k = q - h * 5;
-        if (active && j < cnt) o[k < 4 ? H * D + 4 * h + k : H * D + 4 * H + h] = v[j];
-      }
+        o[k < 4 ? H * D + 4 * h + k : H * D + 4 * H + h] = t;
+      }, active);
     }
   }
 }
@@ -1199,9 +1156,9 @@ bool fwd2_ok(const dgppo_gnn_attn_args* p) {
 
 void fwd2_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
   const int64_t rows = (int64_t)p->G * p->n_agents;
-  const unsigned grid = (unsigned)((rows + fwd2::kRows - 1) / fwd2::kRows);
+  const unsigned grid = (unsigned)((rows + kRows - 1) / kRows);
   const bool no_pre = !(p->xa && p->pre_W);
-  const size_t bytes = ((size_t)fwd2::kRows * fwd2::kQP + kD0 * 32 + 32) * sizeof(float);
+  const size_t bytes = ((size_t)kRows * fwd2::kQP + kD0 * 32 + 32) * sizeof(float);
   if (p->D <= 8 && no_pre) hipLaunchKernelGGL(attn_fwd2r_kernel<8>, dim3(grid), dim3(256), bytes, s, *p);
   else if (p->D <= 16 && no_pre) hipLaunchKernelGGL(attn_fwd2r_kernel<16>, dim3(grid), dim3(256), bytes, s, *p);  // e.g. Omni's 10-wide first layer
   else hipLaunchKernelGGL(attn_fwd2r_kernel<32>, dim3(grid), dim3(256), bytes, s, *p);
@@ -1219,7 +1176,7 @@ void fwd2_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
 // into one partial row per workgroup.  Deterministic: no atomics.
 // ================================================================================================
 namespace bwd2 {
-constexpr int kRows = 16, kSR = 2, kMaxBlocks = 1024;
+constexpr int kSR = 2, kMaxBlocks = 1024;
 // per-head stride HS of the qt / dxbar rows, row pitches, xs pitch (x | x_raw | 1 in pre mode)
 template <int DM>
 struct Lay {
@@ -1248,7 +1205,7 @@ constexpr int kPS = 44;  // chunk staging row: dz (0..31) | x_raw (32..39) | 1 (
 template <int DM>
 size_t lds_floats(int n, int D) {
   using L = bwd2::Lay<DM>;
-  return (size_t)bwd2::kRows * (L::QP + L::GP) + kD0 * 32 + 32 + 4 * 16 * kPS + (size_t)bwd2::kRows * n * D +
+  return (size_t)kRows * (L::QP + L::GP) + kD0 * 32 + 32 + 4 * 16 * kPS + (size_t)kRows * n * D +
          4 * 256;
 }
 }  // namespace bwd2r
@@ -1256,10 +1213,9 @@ size_t lds_floats(int n, int D) {
 template <int DM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void attn_bwd2r_kernel(
     dgppo_gnn_attn_args p, int64_t nblk) {
-  using lanes::f32x4;
   using lanes::wave_sync;
   using LY = bwd2::Lay<DM>;
-  constexpr int kRows = bwd2::kRows, kSR = bwd2::kSR, HS = LY::HS, kQP = LY::QP, kGP = LY::GP;
+  constexpr int kSR = bwd2::kSR, HS = LY::HS, kQP = LY::QP, kGP = LY::GP;
   constexpr int kPS = bwd2r::kPS;
   static_assert(DM == 8 || DM == 16 || DM == 32, "bwd2r instantiations");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1269,7 +1225,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   float* preb = preW + kD0 * 32;    // [32]
   float* stg = preb + 32;           // per wave [16][kPS]: pre-gradient chunk staging
   float* cbi = stg + 4 * 16 * kPS;  // [rows][n][D] agent-sender contributions
-  int* pse = reinterpret_cast<int*>(cbi + bwd2::kRows * p.n_agents * p.D);  // [2 sub-rounds][s, e][256]
+  int* pse = reinterpret_cast<int*>(cbi + kRows * p.n_agents * p.D);  // [2 sub-rounds][s, e][256]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i16 = lane & 15, kq = lane >> 4;
   const int slot = lane >> 5, c = lane & 31;
@@ -1395,28 +1351,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       float xraw[kD0];
 #pragma unroll
       for (int k = 0; k < kD0; ++k) xraw[k] = viapre ? x[k < DM ? k : 0] : 0.0f;
-      if (viapre && !(DGPPO_DIAG_BWD & 1)) {  // relu(x_raw pre_W + pre_b)
-#pragma unroll
-        for (int q = 0; q < DM / 4; ++q) {
-          const f32x4 b = *(const f32x4*)(preb + 4 * q);
-          x[4 * q] = b[0];
-          x[4 * q + 1] = b[1];
-          x[4 * q + 2] = b[2];
-          x[4 * q + 3] = b[3];
-        }
-#pragma unroll
-        for (int k = 0; k < kD0; ++k)
-#pragma unroll
-          for (int q = 0; q < DM / 4; ++q) {
-            const f32x4 w = *(const f32x4*)(preW + k * 32 + 4 * q);
-            x[4 * q] += xraw[k] * w[0];
-            x[4 * q + 1] += xraw[k] * w[1];
-            x[4 * q + 2] += xraw[k] * w[2];
-            x[4 * q + 3] += xraw[k] * w[3];
-          }
-#pragma unroll
-        for (int d = 0; d < DM; ++d) x[d] = x[d] > 0.0f ? x[d] : 0.0f;
-      }
+      if (viapre && !(DGPPO_DIAG_BWD & 1)) pre_row<kD0>(xraw, preW, preb, x);  // as the forward, bit for bit
       // ---- softmax backward
       const float* gv = gs + rl * kGP;
       float dl[kH], dbeta[kH];
@@ -1451,14 +1386,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         float v[DM];
 #pragma unroll
         for (int d = 0; d < DM; ++d) v[d] = dl[h] * x[d];
-        int cnt;
-        const int base = lanes::treduce32(v, cnt);
         float* o = p.dqt + row * dqt_ld(p) + h * D;
-#pragma unroll
-        for (int j = 0; j < lanes::tr_final<DM>(); ++j) {
-          const int q = base + j;
-          if (active && j < cnt && q < D && !(DGPPO_DIAG_BWD & 2)) o[q] = v[j];
-        }
+        wsum(v, [=](int q, float t) { if (q < D && !(DGPPO_DIAG_BWD & 2)) o[q] = t; }, active);
       }
       // ---- sender gradient of this pair: sum_h a_h dxbar_h + dl_h qt_h
       f32x4 cq[DM / 4];
@@ -1517,7 +1446,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
             const float a = i16 <= kD0 ? ws[pp * kPS + 32 + i16] : 0.0f;
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct)
-              gacc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ws[pp * kPS + 16 * ct + i16], gacc[ct], 0, 0, 0);
+              gacc[ct] = mma(a, ws[pp * kPS + 16 * ct + i16], gacc[ct]);
           }
           wave_sync();
         }
@@ -1574,7 +1503,7 @@ bool bwd2_ok(const dgppo_gnn_attn_args* p) {
     const char* e = getenv("DGPPO_ATTN_BWD1");
     return e && atoi(e) != 0;
   }();
-  if (off || p->H != kH || p->C > 32 || p->D > 32 || p->F > 64 || !p->sidx || p->n_agents > bwd2::kRows) return false;
+  if (off || p->H != kH || p->C > 32 || p->D > 32 || p->F > 64 || !p->sidx || p->n_agents > kRows) return false;
   if (p->xa == nullptr) return p->dx == nullptr && p->D <= 32;
   if (p->D0 > kD0) return false;
   if (p->pre_W && p->D > 32) return false;
@@ -1586,7 +1515,7 @@ int64_t bwd2_grid(const dgppo_gnn_attn_args* p, int64_t* nblk) {
   // SIMD), 6 per CU for the narrower ones (512 / 2048 / 4096 measured no different)
   const bool wide = p->D > 16 || (p->xa && p->pre_W);  // the DM = 32 instantiation
   const int64_t cap = wide ? 768 : 1536;
-  const int gpb = bwd2::kRows / p->n_agents;
+  const int gpb = kRows / p->n_agents;
   *nblk = (p->G + gpb - 1) / gpb;
   return *nblk < cap ? *nblk : cap;
 }
@@ -1758,7 +1687,6 @@ __device__ __forceinline__ lanes::f32x4 pre_quad(const float* raw, const float* 
 
 template <int DM>
 __global__ __launch_bounds__(256) void attn_fwd_graph_kernel(dgppo_gnn_attn_args p, int ns, int cp, int slots) {
-  using lanes::f32x4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int XP = gfwd::row_pitch<DM>(), QP = kH * DM + 4;
   constexpr bool V4 = DM == 32;  // float4 logits / weighted sums (rows zero-padded to DM)
@@ -2038,7 +1966,6 @@ __global__ __launch_bounds__(256) void attn_fwd_graph_kernel(dgppo_gnn_attn_args
 // scale and dbeta_h = sum_c dl_h by wave shuffles; dqt_h = sum_c dl_h x_c one output column per lane.
 template <int DM>
 __global__ __launch_bounds__(256) void attn_bwd_graph_kernel(dgppo_gnn_attn_args p, int cp) {
-  using lanes::f32x4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int XP = DM + 1;
   const int n = p.n_agents, N = p.N, D = p.D, F = p.F, C = p.C, H = kH;
@@ -2159,7 +2086,6 @@ __device__ __forceinline__ float sum64(float v) {
 }
 
 __global__ __launch_bounds__(512) void attn_bwd_graph32_kernel(dgppo_gnn_attn_args p) {
-  using lanes::f32x4;
   using lanes::wave_sync;
   using namespace gbwd32;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -2290,7 +2216,7 @@ __global__ __launch_bounds__(512) void attn_bwd_graph32_kernel(dgppo_gnn_attn_ar
 #pragma unroll
         for (int d = 0; d < 32; ++d) v[d] = l0 * x[0][d] + l1 * x[1][d];
         int cnt;
-        const int base = lanes::treduce32(v, cnt);
+        const int base = lanes::treduce32(v, cnt);  // as attn_core.h wsum, with the two halves combined before the store
         const float tot = v[0] + __shfl_xor(v[0], 32, 64);
         if (lane < 32 && cnt > 0 && base < D) p.dqt[row * dqt_ld(p) + h * D + base] = tot;
       }
@@ -2342,7 +2268,7 @@ __global__ __launch_bounds__(512) void attn_bwd_graph32_kernel(dgppo_gnn_attn_ar
               const float a = i16 <= kD0 ? stg[pp * kPS + 32 + i16] : 0.0f;
 #pragma unroll
               for (int ct = 0; ct < 2; ++ct)
-                gacc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, stg[pp * kPS + 16 * ct + i16], gacc[ct], 0, 0, 0);
+                gacc[ct] = mma(a, stg[pp * kPS + 16 * ct + i16], gacc[ct]);
             }
             wave_sync();
           }

@@ -27,14 +27,10 @@
 #include <stdlib.h>
 
 #include "../../include/dgppo_hip.h"
-#include "lanes.h"
+#include "attn_core.h"
 
 namespace dgppo {
 namespace {
-
-using lanes::f32x4;
-
-constexpr int kH = 3, kRows = 16, kD0 = 8;
 
 // DM = 8: full mode (raw node rows, D <= 8); DM = 32: agent mode (D = 32, never-receivers via pre_W)
 template <int DM>
@@ -92,40 +88,6 @@ Carve carve(int gpb, int N, bool agent, bool ytile, bool tail) {
   return c;
 }
 
-__device__ __forceinline__ f32x4 mma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// LayerNorm(64) (eps 1e-6) + ReLU in place over the 16 rows of a [16][kYP] tile: 8 lanes per row (threads 0..127;
-// the others return), flax's mean / E[x^2] - mean^2 form as the GEMM epilogue computes it
-__device__ __forceinline__ void ln_relu64(float* Y, const float* scale, const float* bias) {
-  if (threadIdx.x >= kRows * 8) return;
-  const int r = threadIdx.x >> 3, q = threadIdx.x & 7;
-  float v[8];
-  float s = 0.0f, s2 = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    v[j] = Y[r * kYP + q * 8 + j];
-    s += v[j];
-    s2 += v[j] * v[j];
-  }
-#pragma unroll
-  for (int o = 4; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    s2 += __shfl_xor(s2, o, 64);
-  }
-  const float mean = s / 64.0f;
-  float var = s2 / 64.0f - mean * mean;
-  var = var > 0.0f ? var : 0.0f;
-  const float rstd = 1.0f / sqrtf(var + 1e-6f);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int col = q * 8 + j;
-    const float o = ((v[j] - mean) * rstd) * scale[col] + bias[col];
-    Y[r * kYP + col] = o > 0.0f ? o : 0.0f;
-  }
-}
-
 // acc (16 rows x the wave's 16 columns 16 ct + (lane & 15)) = A (LDS tile [16][lda], K = 64) @ W (64 x ldw, global,
 // columns 16 ct ..); every B operand loaded before the first MFMA
 __device__ __forceinline__ f32x4 dense64(const float* A, int lda, const float* W, int ldw, int ct, int N) {
@@ -139,8 +101,6 @@ __device__ __forceinline__ f32x4 dense64(const float* A, int lda, const float* W
   for (int ks = 0; ks < 16; ++ks) acc = mma(A[i16 * lda + 4 * ks + kq], b[ks], acc);
   return acc;
 }
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 #ifndef DGPPO_DIAG_FWD
 #define DGPPO_DIAG_FWD 0  // diagnostic builds only (time attribution, results invalid): 1 no staging loads, 2 no xbar
@@ -207,27 +167,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 
   for (int t = tid; t < kRows * QP; t += 256) qts[t] = 0.0f;
   __syncthreads();
 
-  // ---- stage 2 (agent mode): never-receivers' rows relu(x_raw pre_W + pre_b), once per node, in attn_fwd2r /
-  // attn_bwd2r's order of operations (bias, then fma over k ascending): the same ReLU gates as their recomputation
+  // ---- stage 2 (agent mode): never-receivers' rows relu(x_raw pre_W + pre_b), once per node, by the
+  // pre-transform attn_fwd2r / attn_bwd2r use (attn_core.h): the same ReLU gates as their recomputation
   if constexpr (agent) {
     const int nn = N - n;
     for (int t = tid; t < ng * nn * (DM / 4); t += 256) {
       const int q = t & (DM / 4 - 1), rr = t / (DM / 4);
       const int g = rr / nn, j = n + rr - g * nn;
       const float* xr = rx + (g * N + j) * kD0;
-      const f32x4 b = *(const f32x4*)(preb + 4 * q);
-      float v0 = b[0], v1 = b[1], v2 = b[2], v3 = b[3];
-#pragma unroll
-      for (int k = 0; k < kD0; ++k) {
-        const float xk = xr[k];
-        const f32x4 w = *(const f32x4*)(preW + k * 32 + 4 * q);
-        v0 += xk * w[0];
-        v1 += xk * w[1];
-        v2 += xk * w[2];
-        v3 += xk * w[3];
-      }
-      *(f32x4*)(xs + (g * N + j) * XP + 4 * q) =
-          f32x4{v0 > 0.0f ? v0 : 0.0f, v1 > 0.0f ? v1 : 0.0f, v2 > 0.0f ? v2 : 0.0f, v3 > 0.0f ? v3 : 0.0f};
+      *(f32x4*)(xs + (g * N + j) * XP + 4 * q) = pre_node<kD0>(xr, preW + 4 * q, preb + 4 * q);
     }
   }
   // ---- stage 3: [qt | beta] = [x_i 1] QBW (16 x (D+1) x W) on MFMA; reads only the receivers' rows (stage 1).
@@ -279,7 +227,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 
   }
   __syncthreads();
 
-  // ---- stage 4: attention core, one half-wave per receiving agent, one lane per candidate (attn_fwd2r's math)
+  // ---- stage 4: attention core, one half-wave per receiving agent, one lane per candidate (attn_core.h, as attn_fwd2r)
   float* xc = rx;  // the raw rows are dead: xcat tile [16][XCP]
   {
     const int slot = lane >> 5, c = lane & 31;
@@ -311,41 +259,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 
       }
       const float* qt = qts + rl * QP;
       float aw[kH];
-#pragma unroll
-      for (int h = 0; h < kH; ++h) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int q = 0; q < DM / 4; ++q)
-          if (q < TQ) {
-            const f32x4 qq = ((const f32x4*)(qt + HS * h))[q];
-            acc += x[4 * q] * qq[0] + x[4 * q + 1] * qq[1] + x[4 * q + 2] * qq[2] + x[4 * q + 3] * qq[3];
-          }
-        const float lg = ok ? (acc + qt[kH * HS + h]) * a.scale : -INFINITY;
-        const float mx = lanes::max32(lg);
-        const float ex = ok ? expf(lg - mx) : 0.0f;
-        const float sm = lanes::sum32(ex);
-        aw[h] = ok ? ex / sm : 0.0f;
-        if (active && c < C && a.attn && !(DGPPO_DIAG_FWD & 8)) a.attn[(row * kH + h) * C + c] = aw[h];
-      }
+      // (the sinks capture locals only: a capture of the kernel argument struct keeps it in memory until the
+      // callback is inlined, which is after its loads would have been marked as never clobbered)
+      float* const attn = (DGPPO_DIAG_FWD & 8) ? nullptr : a.attn;
+      head_weights(x, qt, HS, TQ, a.scale, ok, aw, [=](int h, float w) {
+        if (active && c < C && attn) attn[(row * kH + h) * C + c] = w;
+      });
       float* o = (a.xcat && !(DGPPO_DIAG_FWD & 8)) ? a.xcat + row * WX : nullptr;
       float* ot = xc + rl * XCP;
-      {  // xbar_h = sum_c a_hc x_c by transposed DPP reductions (an LDS loop over the candidates measured slower)
+      const auto put = [=](int col, float t) {
+        ot[col] = t;
+        if (o) o[col] = t;
+      };
+      // xbar_h = sum_c a_hc x_c by transposed DPP reductions (an LDS loop over the candidates measured slower)
 #pragma unroll
-        for (int h = 0; h < ((DGPPO_DIAG_FWD & 2) ? 0 : kH); ++h) {
-          float v[DM];
+      for (int h = 0; h < ((DGPPO_DIAG_FWD & 2) ? 0 : kH); ++h) {
+        float v[DM];
 #pragma unroll
-          for (int dd = 0; dd < DM; ++dd) v[dd] = aw[h] * x[dd];
-          int cnt;
-          const int base = lanes::treduce32(v, cnt);
-#pragma unroll
-          for (int j = 0; j < lanes::tr_final<DM>(); ++j) {
-            const int q = base + j;
-            if (active && j < cnt && q < D) {
-              ot[h * D + q] = v[j];
-              if (o) o[h * D + q] = v[j];
-            }
-          }
-        }
+        for (int dd = 0; dd < DM; ++dd) v[dd] = aw[h] * x[dd];
+        wsum(v, [=](int q, float t) { if (q < D) put(h * D + q, t); }, active);
       }
       {
         float v[NEV];
@@ -355,18 +287,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 
           for (int j = 0; j < 4; ++j) v[h * 5 + j] = aw[h] * ef[j];
           v[h * 5 + 4] = aw[h];
         }
-        int cnt;
-        const int base = lanes::treduce32(v, cnt);
-#pragma unroll
-        for (int j = 0; j < lanes::tr_final<NEV>(); ++j) {
-          const int q = base + j;
+        wsum(v, [=](int q, float t) {
           const int h = q / 5, k = q - h * 5;
-          if (active && j < cnt) {
-            const int col = k < 4 ? kH * D + 4 * h + k : kH * D + 4 * kH + h;
-            ot[col] = v[j];
-            if (o) o[col] = v[j];
-          }
-        }
+          put(k < 4 ? kH * D + 4 * h + k : kH * D + 4 * kH + h, t);
+        }, active);
       }
     }
   }
@@ -463,7 +387,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TAIL ? 3 : 
 #pragma unroll
       for (int i = 0; i < 4; ++i) yt[(4 * kq + i) * kYP + col] = acc[i] + b;
       __syncthreads();
-      ln_relu64(yt, lnp + 128 * l, lnp + 128 * l + 64);
+      ln_relu64<kRows, kYP>(yt, lnp + 128 * l, lnp + 128 * l + 64);
       __syncthreads();
     }
     // GRU: wave w's column tiles w, w+4, w+8 = the r, z, n gates of hidden columns 16w .. 16w+15

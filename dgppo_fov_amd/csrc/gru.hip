@@ -22,14 +22,12 @@
 #include <stdlib.h>
 
 #include "../../include/dgppo_hip.h"
+#include "attn_core.h"
 
 namespace dgppo {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kHid = 64, kG3 = 192, kRows = 16, kWP = 193, kHP = 65, kThreads = 256, kMaxBlocks = 1024;
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+constexpr int kHid = 64, kG3 = 192, kWP = 193, kHP = 65, kThreads = 256, kMaxBlocks = 1024;
 
 // sink for the stores of padding rows (q >= Q): every store stays an unconditional straight-line
 // instruction, so the compiler's wait counts stay exact (a guarded store or load is a branch, after
@@ -55,9 +53,9 @@ __device__ __forceinline__ void gh_tiles(const float* A, const float* Whs, int c
     const int k = 4 * kk + kq;
     const float a = A[i * kHP + k];
     const float* w = Whs + k * kWP + col;
-    ar = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w[0], ar, 0, 0, 0);
-    az = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w[kHid], az, 0, 0, 0);
-    an = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w[2 * kHid], an, 0, 0, 0);
+    ar = mma(a, w[0], ar);
+    az = mma(a, w[kHid], az);
+    an = mma(a, w[2 * kHid], an);
   }
 }
 
@@ -86,9 +84,9 @@ __device__ __forceinline__ void gh_tiles_reg(const float* A, const WhFrag& f, in
 #pragma unroll
   for (int kk = 0; kk < kHid / 4; ++kk) {
     const float a = A[i * kHP + 4 * kk + kq];
-    ar = __builtin_amdgcn_mfma_f32_16x16x4f32(a, f.v[0][kk], ar, 0, 0, 0);
-    az = __builtin_amdgcn_mfma_f32_16x16x4f32(a, f.v[1][kk], az, 0, 0, 0);
-    an = __builtin_amdgcn_mfma_f32_16x16x4f32(a, f.v[2][kk], an, 0, 0, 0);
+    ar = mma(a, f.v[0][kk], ar);
+    az = mma(a, f.v[1][kk], az);
+    an = mma(a, f.v[2][kk], an);
   }
 }
 
@@ -307,12 +305,12 @@ __global__ __launch_bounds__(kThreads) void gru_seq_bwd_kernel(dgppo_gru_seq_arg
       if constexpr (REGB) {
 #pragma unroll
         for (int kk = 0; kk < kG3 / 4; ++kk)
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dg[i * kWP + 4 * kk + kq], wt[kk], acc, 0, 0, 0);
+          acc = mma(dg[i * kWP + 4 * kk + kq], wt[kk], acc);
       } else {
 #pragma unroll 8
         for (int kk = 0; kk < kG3 / 4; ++kk) {
           const int k = 4 * kk + kq;
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dg[i * kWP + k], Whs[col * kWP + k], acc, 0, 0, 0);
+          acc = mma(dg[i * kWP + k], Whs[col * kWP + k], acc);
         }
       }
 #pragma unroll

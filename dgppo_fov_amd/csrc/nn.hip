@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/dgppo_hip.h"
+#include "attn_core.h"
 #include "noise.h"
 
 namespace dgppo {
@@ -32,7 +33,6 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplusf_(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 
 // ---- LayerNorm (+ReLU) over rows of width F (flax LayerNorm, eps 1e-6, fast variance) --------
@@ -278,8 +278,8 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const float* gi, const flo
     const int j = (int)(t - r * H);
     const float* a = gi + r * 3 * H;
     const float* b = gh + r * 3 * H;
-    const float rg = sigmoidf_(a[j] + b[j]);
-    const float zg = sigmoidf_(a[H + j] + b[H + j]);
+    const float rg = sigm(a[j] + b[j]);
+    const float zg = sigm(a[H + j] + b[H + j]);
     const float ng = tanhf(a[2 * H + j] + rg * (b[2 * H + j] + bhn[j]));
     hn_out[t] = (1.0f - zg) * ng + zg * h[t];
   }
@@ -295,8 +295,8 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const float* gi, const flo
     const int j = (int)(t - r * H);
     const float* a = gi + r * 3 * H;
     const float* b = gh + r * 3 * H;
-    const float rg = sigmoidf_(a[j] + b[j]);
-    const float zg = sigmoidf_(a[H + j] + b[H + j]);
+    const float rg = sigm(a[j] + b[j]);
+    const float zg = sigm(a[H + j] + b[H + j]);
     const float hnp = b[2 * H + j] + bhn[j];
     const float ng = tanhf(a[2 * H + j] + rg * hnp);
     const float g = dhn[t];
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void tanh_normal_kernel(dgppo_tanh_normal_args
         const float gen = p.dentropy ? p.dentropy[r] : 0.0f;
         const float dsd_tot = glp * dsd + gen * dsd_e;
         p.dmean[k] = glp * dmu + gen * dmu_e;
-        p.dstd_raw[k] = dsd_tot * sigmoidf_(sraw);
+        p.dstd_raw[k] = dsd_tot * sigm(sraw);
       }
     }
     if (p.log_pi) p.log_pi[r] = lp_sum;
@@ -764,8 +764,6 @@ static int grid_for(int64_t n) {
 // flax.linen.LSTMCell gate math for one step of `rows` carries (the --use-lstm option, dgppo/nn/rnn.py:15-30):
 // g (rows, 4H) = [i | f | g | o] pre-activations (x W_i + h W_h + b, from the GEMMs) -> activated in place;
 // c' = f c + i g, h' = o tanh(c').  A thread per (row, column); the gate columns of a row are H apart.
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(int64_t rows, int H, float* __restrict__ g,
                                                             const float* __restrict__ c_prev, float* __restrict__ c_out,
                                                             float* __restrict__ h_out) {

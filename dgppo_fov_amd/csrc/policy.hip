@@ -4,7 +4,7 @@
 //   GNN (GraphTransformer x L, per receiving agent) -> MLP head (Dense+LN+ReLU x 2) -> GRUCell ->
 //   ScaleHid -> mean / std Dense -> TanhNormal sample (or mode) + log-prob
 //
-// A 256-thread workgroup owns kRowsG = 16 agent rows (16 / n whole graphs) and keeps every activation of the
+// A 256-thread workgroup owns kRows = 16 agent rows (16 / n whole graphs) and keeps every activation of the
 // chain in LDS: the ~20 launches and HBM round trips of the unfused step collapse into one kernel
 // whose HBM traffic is the graph rows it gathers, the carries and the outputs.  The kernel is
 // latency-bound (a chain of dependent gathers and small GEMMs per workgroup), so the design
@@ -31,21 +31,17 @@
 #include <string.h>
 
 #include "../../include/dgppo_hip.h"
-#include "lanes.h"
+#include "attn_core.h"
 #include "noise.h"
 
 namespace dgppo {
 namespace {
 
-using lanes::f32x4;
 using lanes::wave_sync;
-__device__ __forceinline__ float gsum32(float v) { return lanes::sum32(v); }
-__device__ __forceinline__ float gmax32(float v) { return lanes::max32(v); }
-__device__ __forceinline__ float gsum8(float v) { return lanes::sum8(v); }
 
-constexpr int kRowsG = 16, kThreads = 256, kHeads = 3, kHid = 64;
+constexpr int kThreads = 256, kHid = 64;
 // row tiles of 16, attention sub-rounds (a wave takes two rows per sub-round), pairs per thread
-constexpr int kRT = kRowsG / 16, kSR = kRowsG / 8;
+constexpr int kRT = kRows / 16, kSR = kRows / 8;
 // raw node rows up to 12 wide and edge rows up to 4 + 6 (LidarOmniTarget: 10 / 10); the kernel is
 // instantiated narrow (<= 8, 4: the Lidar / MPE envs, 240 VGPRs = 2 waves per SIMD) and wide
 constexpr int kMaxD0 = 12, kMaxEX = 6, kCP = 32;
@@ -78,7 +74,6 @@ constexpr int kQKRows = 33, kQKCols = kQTP, kQKStride = kQKRows * kQKCols;
   } while (0)
 #endif
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplusf(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float log_ndtr(float z) {
   if (z > -10.0f) return logf(0.5f * erfcf(-z * 0.70710678118654752f));
@@ -142,7 +137,7 @@ __device__ __forceinline__ void frag_mma(f32x4 (&acc)[CT][kRT], const float* A, 
     for (int t = 0; t < CT; ++t)
 #pragma unroll
       for (int rt = 0; rt < kRT; ++rt)
-        acc[t][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt], f.v[ks][t], acc[t][rt], 0, 0, 0);
+        acc[t][rt] = mma(a[rt], f.v[ks][t], acc[t][rt]);
   }
 }
 
@@ -186,27 +181,27 @@ struct Lds {
 };
 
 // the register form's att region only hosts the pair tables (before the GNN) and the carries (after it)
-constexpr int kAttReg = kRowsG * kYP > 2 * kRowsG * kCP ? kRowsG * kYP : 2 * kRowsG * kCP;
+constexpr int kAttReg = kRows * kYP > 2 * kRows * kCP ? kRows * kYP : 2 * kRows * kCP;
 constexpr size_t lds_floats() {
-  return (size_t)kRowsG * (kX0P + kQTP + kXCP + kY0P + kYP) + kMaxD0 * 32 + 32 + 4 * kHid + 2 * kHid * 4 + 8 +
+  return (size_t)kRows * (kX0P + kQTP + kXCP + kY0P + kYP) + kMaxD0 * 32 + 32 + 4 * kHid + 2 * kHid * 4 + 8 +
          kAttReg + kPreMax * 32;
 }
 
 __device__ __forceinline__ Lds carve(float* base) {
   Lds L;
   L.x0 = base;
-  L.qt = L.x0 + kRowsG * kX0P;
-  L.xc = L.qt + kRowsG * kQTP;
-  L.y0 = L.xc + kRowsG * kXCP;
-  L.yb = L.y0 + kRowsG * kY0P;
-  L.preW = L.yb + kRowsG * kYP;
+  L.qt = L.x0 + kRows * kX0P;
+  L.xc = L.qt + kRows * kQTP;
+  L.y0 = L.xc + kRows * kXCP;
+  L.yb = L.y0 + kRows * kY0P;
+  L.preW = L.yb + kRows * kYP;
   L.preb = L.preW + kMaxD0 * 32;
   L.lnp = L.preb + 32;           // ln0 scale, ln0 bias, ln1 scale, ln1 bias (64 each)
   L.outW = L.lnp + 4 * kHid;     // [Wm | Wsd] (64 x 2A, A <= 4) then bm, bsd
   L.att = L.outW + 2 * kHid * 4 + 8;
   L.psrc = (int*)L.att;
   L.hb = L.att;
-  L.pedge = L.psrc + kRowsG * kCP;
+  L.pedge = L.psrc + kRows * kCP;
   L.pre = L.att + kAttReg;  // (register form only)
   return L;
 }
@@ -282,9 +277,9 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
                                              const PairG<MD0, MEX> (&pg)[kSR], const Lds& L, const float* qk,
                                              const float* A, int lda, float* out, int ldo, int nmag, int pk) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n = p.n_agents, D = ly.D, F = ly.F, H = kHeads;
+  const int n = p.n_agents, D = ly.D, F = ly.F, H = kH;
   const int EX = MEX > 0 ? p.ED - 4 : 0;
-  // [QT_h | beta_h] = A QK + qk_bias (kRowsG x 100)
+  // [QT_h | beta_h] = A QK + qk_bias (kRows x 100)
   {
     Frag<KQ, 2> fq;
     float bq[2];
@@ -297,12 +292,12 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
   }
   __syncthreads();
   PROBE(pk);
-  const int slot = lane >> 5, c = lane & 31;
+  const int slot = lane >> 5;
   const float scale = rsqrtf((float)F);
   // x width DX: layer 0 the raw row (MD0), layer 1 the 32-wide hidden row.  Per head the DX weighted x
   // sums are one transposed reduction; the edge / sig sums of all heads ([ebar_h (4) | sig_h | ebar_x_h
   // (EX)] x 3) a second one, so at most DX + DX values are live
-  constexpr int NE = 5 + MEX, NEV = kHeads * NE;
+  constexpr int NE = 5 + MEX, NEV = kH * NE;
 #pragma unroll
   for (int sr = 0; sr < kSR; ++sr) {  // unrolled: pg[sr] read directly, pg[0] dies after the first sub-round
     const PairG<MD0, MEX>& cur = pg[sr];
@@ -334,35 +329,15 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
         x[4 * q + 3] = v[3];
       }
     } else {  // never-receiving sender: relu(x_raw Wu0 + bu0) (masked pairs too; their weights are 0)
-#pragma unroll
-      for (int q = 0; q < DX / 4; ++q) {
-        const f32x4 b = *(const f32x4*)(L.preb + 4 * q);
-        x[4 * q] = b[0];
-        x[4 * q + 1] = b[1];
-        x[4 * q + 2] = b[2];
-        x[4 * q + 3] = b[3];
-      }
-#pragma unroll
-      for (int k = 0; k < (DGPPO_DIAG_POL ? 0 : MD0); ++k) {
-        const float xk = cur.xr[k];
-#pragma unroll
-        for (int q = 0; q < DX / 4; ++q) {
-          const f32x4 w = *(const f32x4*)(L.preW + k * 32 + 4 * q);
-          x[4 * q] += xk * w[0];
-          x[4 * q + 1] += xk * w[1];
-          x[4 * q + 2] += xk * w[2];
-          x[4 * q + 3] += xk * w[3];
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < DX; ++d) x[d] = x[d] > 0.0f ? x[d] : 0.0f;
+      pre_row<DGPPO_DIAG_POL ? 0 : MD0>(cur.xr, L.preW, L.preb, x);
     }
-    // logits (QT_h . x + beta_h) / sqrt(F) and the softmax over the row's 32 candidates
+    // logits (QT_h . x + beta_h) / sqrt(F) and the softmax over the row's 32 candidates: attn_core.h head_weights
+    // written out (through the helper this kernel's register allocation changes: policy_step<8, 0, true> 2% slower)
     const float* qt = L.qt + r * kQTP;
     float* o = L.xc + r * kXCP;
-    float aw[kHeads];
+    float aw[kH];
 #pragma unroll
-    for (int h = 0; h < kHeads; ++h) {
+    for (int h = 0; h < kH; ++h) {
       float acc = 0.0f;
 #pragma unroll
       for (int q = 0; q < DX / 4; ++q) {
@@ -370,14 +345,14 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
         acc += x[4 * q] * qv[0] + x[4 * q + 1] * qv[1] + x[4 * q + 2] * qv[2] + x[4 * q + 3] * qv[3];
       }
       const float lg = ok ? (acc + qt[96 + h]) * scale : -INFINITY;
-      const float mx = gmax32(lg);
+      const float mx = lanes::max32(lg);
       const float ex = ok ? expf(lg - mx) : 0.0f;
-      const float sm = gsum32(ex);
+      const float sm = lanes::sum32(ex);
       aw[h] = ok ? ex / sm : 0.0f;
     }
-    // xbar_h = sum_c a_h x_c
+    // xbar_h = sum_c a_h x_c: attn_core.h wsum written out (same reason), as the [ebar | sig] sums below
 #pragma unroll
-    for (int h = 0; h < kHeads; ++h) {
+    for (int h = 0; h < kH; ++h) {
       float v[DX];
 #pragma unroll
       for (int d = 0; d < DX; ++d) v[d] = aw[h] * x[d];
@@ -393,7 +368,7 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
     {
       float v[NEV];
 #pragma unroll
-      for (int h = 0; h < kHeads; ++h) {
+      for (int h = 0; h < kH; ++h) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[h * NE + j] = aw[h] * cur.ef[j];
         v[h * NE + 4] = aw[h];
@@ -424,8 +399,8 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
   Frag<KX, 1> fx;
   Frag<KU, 1> fu;
   float bu[1];
-  frag_load(fc, ly.Wcat, ly.F, kHeads * (ly.D + 5));
-  frag_load(fx, ly.Wex, ly.F, EX > 0 ? kHeads * EX : 0);
+  frag_load(fc, ly.Wcat, ly.F, kH * (ly.D + 5));
+  frag_load(fx, ly.Wex, ly.F, EX > 0 ? kH * EX : 0);
   frag_load(fu, ly.Wu, ly.F, ly.D);
   bias_load(bu, ly.bu, ly.F);
   {
@@ -441,35 +416,6 @@ __device__ __forceinline__ void gt_layer_reg(const dgppo_policy_step_args& p, co
   __syncthreads();
 }
 
-// in-place LayerNorm (eps 1e-6) + ReLU over 64 columns of the kRowsG rows: 8 lanes per row
-__device__ __forceinline__ void ln_relu64(float* Y, const float* scale, const float* bias) {
-  if (threadIdx.x >= kRowsG * 8) return;  // whole waves
-  const int r = threadIdx.x >> 3, q = threadIdx.x & 7;
-  float v[8];
-  float s = 0.0f, s2 = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    v[j] = Y[r * kYP + q * 8 + j];
-    s += v[j];
-    s2 += v[j] * v[j];
-  }
-#pragma unroll
-  for (int o = 4; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    s2 += __shfl_xor(s2, o, 64);
-  }
-  const float mean = s / 64.0f;
-  float var = s2 / 64.0f - mean * mean;
-  var = var > 0.0f ? var : 0.0f;
-  const float rstd = 1.0f / sqrtf(var + 1e-6f);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int col = q * 8 + j;
-    const float o = (v[j] - mean) * rstd * scale[col] + bias[col];
-    Y[r * kYP + col] = o > 0.0f ? o : 0.0f;
-  }
-}
-
 // NP: the per-node layer-1 pre-transform table (narrow register form, two layers, <= kPreMax never-receiving nodes
 // per group: the host picks this instantiation, node_pre_ok); its own instantiation, so that the raw sender rows die
 // after layer 0 instead of staying live through layer 1 for the per-lane fallback
@@ -481,7 +427,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
   const int i16 = lane & 15, kq = lane >> 4;
   const int n = p.n_agents, A = p.A;
   const int nmag = 65536 / n + 1;
-  const int gpg = kRowsG / n;  // graphs per row group
+  const int gpg = kRows / n;  // graphs per row group
   const int64_t ngroups = (p.G + gpg - 1) / gpg;
   const bool two = p.n_layers == 2;
   // one row group per workgroup (a persistent loop would let LICM hoist every weight load into
@@ -494,14 +440,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
   const int64_t row0 = g0 * n;
   PROBE(0);
   // ---- level 1 loads: candidate edges, agent rows, carries, small parameters, weight fragments
-  constexpr int kPT = kRowsG * kCP / kThreads;  // pairs per thread
+  constexpr int kPT = kRows * kCP / kThreads;  // pairs per thread
   int ed[kPT];
 #pragma unroll
   for (int u = 0; u < kPT; ++u) {
     const int e = threadIdx.x + u * kThreads, r = e / kCP, c = e % kCP;
     ed[u] = (r < rows && c < p.C) ? p.cand[(r - div_n(r, nmag) * n) * p.C + c] : -1;
   }
-  for (int e = threadIdx.x; e < kRowsG * kMaxD0; e += kThreads) {
+  for (int e = threadIdx.x; e < kRows * kMaxD0; e += kThreads) {
     const int r = e / kMaxD0, k = e % kMaxD0;
     float v = 0.0f;
     const int gl = div_n(r, nmag);
@@ -509,7 +455,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
     L.x0[r * kX0P + k] = v;
   }
   // carries: held in registers until the GNN has released the attention scratch they go to
-  constexpr int kHT = kRowsG * kHid / kThreads;
+  constexpr int kHT = kRows * kHid / kThreads;
   float hreg[kHT];
 #pragma unroll
   for (int u = 0; u < kHT; ++u) {
@@ -582,8 +528,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
       f32x4 acc = {b, b, b, b};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(L.xc[(16 * tile + i16) * kNarrowD0 + 4 * ks + kq],
-                                                   L.preW[(4 * ks + kq) * 32 + 16 * ct + i16], acc, 0, 0, 0);
+        acc = mma(L.xc[(16 * tile + i16) * kNarrowD0 + 4 * ks + kq], L.preW[(4 * ks + kq) * 32 + 16 * ct + i16], acc);
       const int col = 16 * ct + i16;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -603,8 +548,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
   PROBE(1);
   // ---- GNN
   {
-    constexpr int KX = MEX > 0 ? (kHeads * MEX + 3) / 4 : 1;
-    gt_layer_reg<MD0, true, MD0, MEX, (MD0 + 3) / 4, (kHeads * (MD0 + 5) + 3) / 4, KX, (MD0 + 3) / 4>(
+    constexpr int KX = MEX > 0 ? (kH * MEX + 3) / 4 : 1;
+    gt_layer_reg<MD0, true, MD0, MEX, (MD0 + 3) / 4, (kH * (MD0 + 5) + 3) / 4, KX, (MD0 + 3) / 4>(
         p, p.layer[0], pg, L, p.work, L.x0, kX0P, two ? L.y0 : L.yb, two ? kY0P : kYP, nmag, 2);
     PROBE(4);
     if (two) {
@@ -641,7 +586,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
     __syncthreads();
     acc_store(acc, L.yb, kYP, kHid, bh0, 1.0f, false);
     __syncthreads();
-    ln_relu64(L.yb, L.lnp, L.lnp + kHid);
+    ln_relu64<kRows, kYP>(L.yb, L.lnp, L.lnp + kHid);
     __syncthreads();
     frag_load(fi, p.gru_Wi, 3 * kHid, kHid);
     acc_zero(acc);
@@ -649,7 +594,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
     __syncthreads();
     acc_store(acc, L.yb, kYP, kHid, bh1, 1.0f, false);
     __syncthreads();
-    ln_relu64(L.yb, L.lnp + 2 * kHid, L.lnp + 3 * kHid);
+    ln_relu64<kRows, kYP>(L.yb, L.lnp + 2 * kHid, L.lnp + 3 * kHid);
     __syncthreads();
   }
   PROBE(8);
@@ -699,7 +644,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
   PROBE(10);
   // ---- mean / std heads + TanhNormal (policy.py:61-74, distribution.py:24-35): 8 lanes per row,
   // each summing 8 of the 64 features for all 2A outputs, then lane j < A finishes action dim j
-  if (threadIdx.x < kRowsG * 8) {  // whole waves
+  if (threadIdx.x < kRows * 8) {  // whole waves
     float part[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) part[j] = 0.0f;
@@ -712,7 +657,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
         if (j < 2 * A) part[j] += sv * L.outW[k * 2 * A + j];
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) part[j] = gsum8(part[j]);
+    for (int j = 0; j < 8; ++j) part[j] = lanes::sum8(part[j]);
     float mu = 0.0f, sraw = 0.0f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -740,7 +685,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MD0 <=
     }
     if (tq >= A) lp = 0.0f;
     // sum over the action dims of the row (lanes tq < A of the 8-lane group)
-    const float tot = gsum8(lp);
+    const float tot = lanes::sum8(lp);
     if (tr < rows && tq < A) {
       p.action[(row0 + tr) * A + tq] = act;
       if (tq == 0 && p.log_pi) p.log_pi[row0 + tr] = tot;
@@ -759,10 +704,10 @@ __global__ __launch_bounds__(256) void policy_prepare_kernel(dgppo_policy_step_a
   const int k = idx / kQKCols, col = idx % kQKCols;
   const int D = ly.D, F = ly.F;
   float v = 0.0f;
-  if ((k < D || k == 32) && col < 96 + kHeads) {
+  if ((k < D || k == 32) && col < 96 + kH) {
     const int h = col < 96 ? col / 32 : col - 96, d = col < 96 ? col % 32 : 0;
     if (col >= 96 || d < D) {
-      const float* q = k < D ? ly.Wq + (int64_t)k * kHeads * F + h * F : ly.bq + h * F;
+      const float* q = k < D ? ly.Wq + (int64_t)k * kH * F + h * F : ly.bq + h * F;
       for (int f = 0; f < F; ++f)
         v += q[f] * (col < 96 ? ly.Wkt[((int64_t)h * F + f) * D + d] : ly.bk[h * F + f]);
     }
@@ -777,8 +722,8 @@ size_t lds_bytes() { return lds_floats() * sizeof(float); }
 
 extern "C" int dgppo_policy_step_supported(const dgppo_policy_step_args* p) {
   if (!p) return 0;
-  if (p->n_agents < 1 || p->n_agents > dgppo::kRowsG || p->C < 1 || p->C > dgppo::kCP || p->D0 < 1 ||
-      p->D0 > dgppo::kMaxD0 || p->A < 1 || p->A > 4 || p->H != dgppo::kHeads || p->ED < 4 ||
+  if (p->n_agents < 1 || p->n_agents > dgppo::kRows || p->C < 1 || p->C > dgppo::kCP || p->D0 < 1 ||
+      p->D0 > dgppo::kMaxD0 || p->A < 1 || p->A > 4 || p->H != dgppo::kH || p->ED < 4 ||
       p->ED > 4 + dgppo::kMaxEX)
     return 0;
   for (int l = 0; l < p->n_layers && l < 2; ++l)
@@ -803,7 +748,7 @@ extern "C" int dgppo_policy_step(const dgppo_policy_step_args* p, void* stream) 
       !p->h_in || !p->h_out || !p->action || (p->mode == 1 && !p->noise && !p->noise_seed) || !p->work || p->G < 0)
     return DGPPO_EINVAL;
   if (p->G == 0) return 0;
-  const int gpg = dgppo::kRowsG / p->n_agents;
+  const int gpg = dgppo::kRows / p->n_agents;
   const int64_t ngroups = (p->G + gpg - 1) / gpg;
   if (ngroups > INT32_MAX) return DGPPO_EINVAL;
   const int64_t grid = ngroups;
