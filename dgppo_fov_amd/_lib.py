@@ -253,6 +253,16 @@ class GnnAttnArgs(ctypes.Structure):
     ]
 
 
+class GnnAttnPlan(ctypes.Structure):  # dgppo_gnn_attn_plan_info
+    FAMILIES = ("FWD2R", "BWD2R", "GRAPH_FWD", "GRAPH_BWD", "GRAPH_BWD32", "BLOCK", "WAVE")  # DGPPO_GNN_ATTN_*
+    _fields_ = [(n, ctypes.c_int32) for n in ("family", "dm", "cp", "gpb", "wfloats", "ns", "slots", "threads")] + \
+               [(n, ctypes.c_int64) for n in ("grid", "nblk", "lds_bytes")]
+
+    @property
+    def family_name(self) -> str:
+        return self.FAMILIES[self.family] if self.family >= 0 else "NONE"
+
+
 class GnnValueTail(ctypes.Structure):  # ABI 11 dgppo_gnn_value_tail
     _fields_ = [
         ("W0", c_f32p), ("b0", c_f32p), ("ln0_s", c_f32p), ("ln0_b", c_f32p),
@@ -346,6 +356,7 @@ SIGNATURES = {
     "dgppo_gru_bwd": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I64, _I32, _V]),
     "dgppo_gru_seq_blocks": (ctypes.c_int64, [_I32]),
     "dgppo_gnn_attn_partial_blocks": (ctypes.c_int64, [_V]),
+    "dgppo_gnn_attn_plan": (ctypes.c_int, [ctypes.POINTER(GnnAttnArgs), _I32, ctypes.POINTER(GnnAttnPlan)]),
     "dgppo_gemm_partial_rows": (ctypes.c_int64, [ctypes.POINTER(GemmArgs)]),
     "dgppo_policy_step_supported": (ctypes.c_int, [_V]),
     "dgppo_policy_work_floats": (ctypes.c_int64, []),

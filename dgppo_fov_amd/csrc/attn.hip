@@ -574,68 +574,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(dgppo_gnn_attn_args p, in
   }
 }
 
-
-// ---- raw gather / transform split (wave kernels prefetch the next sub-round's raw rows) ----------
-typedef const __attribute__((address_space(4))) float* cfloat_p;  // uniform reads -> scalar loads
-
-template <int DM>
-struct Gath {
-  Cand k;
-  float x[DM];   // agent row / full-mode row (or transformed row after finish())
-  float x0[kD0]; // raw row of a transformed sender
-  float ef[4];
-  bool via_pre;
-};
-
-template <int DM>
-__device__ __forceinline__ void gath_load(const dgppo_gnn_attn_args& p, int64_t g, int i, int c, bool active, int D,
-                                          Gath<DM>& r) {
-  r.k = active ? candidate(p, g, i, c) : Cand{-1, -1};
-  const int s = r.k.s;
-  const bool ok = s >= 0;
-  r.via_pre = false;
-#pragma unroll
-  for (int k = 0; k < kD0; ++k) r.x0[k] = 0.0f;
-  if (p.xa == nullptr) {
-    load_row<DM>(p.x + g * p.x_gstride + (int64_t)(ok ? s : 0) * D, D, ok, r.x);
-  } else if (!ok || s < p.n_agents) {
-    load_row<DM>(p.xa + g * p.xa_gstride + (int64_t)(ok ? s : 0) * D, D, ok, r.x);
-  } else {
-    const float* xr = p.x + g * p.x_gstride + (int64_t)s * p.D0;
-#pragma unroll
-    for (int k = 0; k < kD0; ++k) r.x0[k] = k < p.D0 ? xr[k] : 0.0f;
-    r.via_pre = p.pre_W != nullptr;
-#pragma unroll
-    for (int d = 0; d < DM; ++d) r.x[d] = 0.0f;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) r.ef[j] = ok ? p.ef[g * p.ef_gstride + (int64_t)r.k.e * 4 + j] : 0.0f;
-}
-
-// non-agent senders of agent mode: relu(x0 pre_W + pre_b) (or the raw row itself without pre_W)
-template <int DM>
-__device__ __forceinline__ void gath_finish(const dgppo_gnn_attn_args& p, const float* preW, const float* preb,
-                                            Gath<DM>& r) {
-  if (p.xa == nullptr || r.k.s < p.n_agents) return;
-  if (!r.via_pre) {
-#pragma unroll
-    for (int d = 0; d < DM; ++d) r.x[d] = d < kD0 ? r.x0[d < kD0 ? d : 0] : 0.0f;
-    return;
-  }
-#pragma unroll
-  for (int d = 0; d < DM; ++d) {
-    float v = preb[d];
-#pragma unroll
-    for (int k = 0; k < kD0; ++k) v += r.x0[k] * preW[k * DM + d];
-    r.x[d] = v > 0.0f ? v : 0.0f;
-  }
-}
-
 // ================================================================================================
-// Wave-independent kernels (CP <= 64): each WAVE owns whole graphs and walks their receivers RW =
+// Wave-independent backward (CP <= 64): each WAVE owns whole graphs and walks their receivers RW =
 // 64 / CP at a time, with all its LDS images private, so waves never wait on each other (no block
 // barriers inside the loops; the hardware interleaves the waves' gathers).  Block barriers only at
-// start (pre_W staging) and end (pre-gradient combine).
+// start (pre_W staging) and end (pre-gradient combine).  (Its forward twin was measured slower than
+// the block forward and is removed.)
 // ================================================================================================
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -643,8 +587,8 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// per-wave LDS (floats): qt [RW][QP] | g [RW][GP] (bwd) | xs [RW*CR][XP] | a [RW*CR][kH]
-//   | ef [RW*CR][4] | x0s [RW*CR][kD0+1] (bwd) | cb [gpw][n][DM] (bwd)
+// per-wave LDS (floats): qt [RW][QP] | g [RW][GP] | xs [RW*CR][XP] | a [RW*CR][kH]
+//   | ef [RW*CR][4] | x0s [RW*CR][kD0+1] | cb [gpw][n][DM] (cbf floats)
 template <int CP, int DM>
 struct WaveCarve {
   static constexpr int RW = 64 / CP;
@@ -652,19 +596,17 @@ struct WaveCarve {
   static constexpr int QP = kH * DM;
   static constexpr int GP = kH * DM + 16;  // dxbar (H*DM) | debar (kH*4) | dsig (kH) | pad
   float *qt, *g, *xs, *a, *ef, *x0s, *cb;
-  __device__ WaveCarve(float* base, int CR, int cbf, bool bwd) {
+  __device__ WaveCarve(float* base, int CR) {
     qt = base;
     g = qt + RW * QP;
-    xs = g + (bwd ? RW * GP : 0);
+    xs = g + RW * GP;
     a = xs + RW * CR * XP;
     ef = a + RW * CR * kH;
     x0s = ef + RW * CR * 4;
-    cb = x0s + (bwd ? RW * CR * (kD0 + 1) : 0);
-    (void)cbf;
+    cb = x0s + RW * CR * (kD0 + 1);
   }
-  static size_t floats(int CR, int cbf, bool bwd) {
-    size_t f = (size_t)RW * QP + (size_t)RW * CR * (XP + kH + 4);
-    if (bwd) f += (size_t)RW * GP + (size_t)RW * CR * (kD0 + 1) + cbf;
+  static size_t floats(int CR, int cbf) {
+    const size_t f = (size_t)RW * (QP + GP) + (size_t)RW * CR * (XP + kH + 4 + kD0 + 1) + cbf;
     return (f + 3) & ~(size_t)3;
   }
 };
@@ -673,137 +615,6 @@ struct WaveCarve {
 template <int DM>
 constexpr int wave_header_floats() {
   return ((kD0 * DM + DM) + 3) & ~3;
-}
-
-template <int CP, int DM>
-__global__ __launch_bounds__(256) void attn_fwd_wave_kernel(dgppo_gnn_attn_args p, int gpw, int64_t nitems,
-                                                            int wfloats) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  using CV = WaveCarve<CP, DM>;
-  constexpr int RW = CV::RW, XP = CV::XP, QP = CV::QP;
-  const int n = p.n_agents, D = p.D, F = p.F, C = p.C, H = p.H;
-  const int CR = cand_rows(C, CP);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  CV L(lds + wave_header_floats<DM>() + wave * wfloats, CR, 0, false);
-  const int W = H * (D + 5);
-  const int slot = lane / CP, c = lane % CP;
-  const int lr = slot * CR + c;
-  float* preW = lds;
-  float* preb = preW + kD0 * DM;
-  stage_pre(p, preW, preb, DM);
-  __syncthreads();
-  const int64_t gw = (int64_t)blockIdx.x * 4 + wave, nw = (int64_t)gridDim.x * 4;
-  // this wave's sub-rounds j = (its k-th item, r0): a flat sequence so the next one's gathers are
-  // issued while the current one computes
-  const int spi = (gpw * n + RW - 1) / RW;
-  const int64_t my_items = gw < nitems ? (nitems - gw + nw - 1) / nw : 0;
-  const int64_t J = my_items * spi;
-  auto sub = [&](int64_t j, int64_t& g0, int& nrec, int& r0) {
-    const int64_t item = gw + (j / spi) * nw;
-    g0 = item * gpw;
-    const int ng = (int)((int64_t)p.G - g0 < gpw ? (int64_t)p.G - g0 : gpw);
-    nrec = ng * n;
-    r0 = (int)(j % spi) * RW;
-  };
-  Gath<DM> cur, nxt;
-  if (J > 0) {
-    int64_t g0;
-    int nrec, r0;
-    sub(0, g0, nrec, r0);
-    const int rl = r0 + slot;
-    gath_load<DM>(p, g0 + (rl < nrec ? rl / n : 0), rl < nrec ? rl % n : 0, c, rl < nrec, D, cur);
-  }
-  for (int64_t j = 0; j < J; ++j) {
-    int64_t g0;
-    int nrec, r0;
-    sub(j, g0, nrec, r0);
-    const int rl = r0 + slot;
-    const bool active = rl < nrec;
-    const int64_t row = g0 * n + rl;
-    // this sub-round's small loads first (in-order completion), then the next sub-round's gathers
-    float qv[(RW * kH * DM + 63) / 64];
-#pragma unroll
-    for (int u = 0; u < (RW * kH * DM + 63) / 64; ++u) {
-      const int e = lane + 64 * u, rr = e / (H * D), kk = e - rr * (H * D);
-      qv[u] = (e < RW * H * D && r0 + rr < nrec) ? p.qt[(g0 * n + r0 + rr) * qt_ld(p) + kk] : 0.0f;
-    }
-    float bacc[kH];
-#pragma unroll
-    for (int h = 0; h < kH; ++h) {
-      float acc = 0.0f;
-      if (active && h < H)
-        acc = q_dot_bk(p, row, h, c, CP);
-      bacc[h] = acc;
-    }
-    if (j + 1 < J) {
-      int64_t g0n;
-      int nrecn, r0n;
-      sub(j + 1, g0n, nrecn, r0n);
-      const int rln = r0n + slot;
-      gath_load<DM>(p, g0n + (rln < nrecn ? rln / n : 0), rln < nrecn ? rln % n : 0, c, rln < nrecn, D, nxt);
-    }
-#pragma unroll
-    for (int u = 0; u < (RW * kH * DM + 63) / 64; ++u) {
-      const int e = lane + 64 * u, rr = e / (H * D), kk = e - rr * (H * D);
-      if (e < RW * H * D) L.qt[rr * QP + kk] = qv[u];
-    }
-    float beta[kH];
-#pragma unroll
-    for (int h = 0; h < kH; ++h) beta[h] = group_sum<CP>(bacc[h], nullptr);
-    gath_finish<DM>(p, preW, preb, cur);
-    const bool ok = cur.k.s >= 0;
-    wave_sync();
-    float lg[kH], mx[kH], a[kH];
-#pragma unroll
-    for (int h = 0; h < kH; ++h) {
-      float acc = 0.0f;
-      const float* qt = L.qt + slot * QP + h * D;
-#pragma unroll
-      for (int d = 0; d < DM; ++d)
-        if (d < D) acc += qt[d] * cur.x[d];
-      lg[h] = (ok && h < H) ? (acc + beta[h]) * p.scale : -INFINITY;
-      mx[h] = group_max<CP>(lg[h], nullptr);
-    }
-#pragma unroll
-    for (int h = 0; h < kH; ++h) {
-      const float ex = ok && h < H ? expf(lg[h] - mx[h]) : 0.0f;
-      const float sm = group_sum<CP>(ex, nullptr);
-      a[h] = ok && h < H ? ex / sm : 0.0f;
-      if (active && c < C && h < H && p.attn) p.attn[(row * H + h) * C + c] = a[h];
-    }
-    if (c < CR) {
-#pragma unroll
-      for (int d = 0; d < DM; ++d) L.xs[lr * XP + d] = cur.x[d];
-#pragma unroll
-      for (int h = 0; h < kH; ++h) L.a[lr * kH + h] = a[h];
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) L.ef[lr * 4 + jj] = cur.ef[jj];
-    }
-    wave_sync();
-    if (active) {
-      const int base = slot * CR;
-      float* out = p.xcat + row * W;
-      for (int o = c; o < W; o += CP) {
-        float acc = 0.0f;
-        if (o < H * D) {
-          const int h = o / D, d = o - h * D;
-          #pragma unroll 8
-          for (int cc = 0; cc < CR; ++cc) acc += L.a[(base + cc) * kH + h] * L.xs[(base + cc) * XP + d];
-        } else if (o < H * D + 4 * H) {
-          const int q = o - H * D, h = q >> 2, jj = q & 3;
-          #pragma unroll 8
-          for (int cc = 0; cc < CR; ++cc) acc += L.a[(base + cc) * kH + h] * L.ef[(base + cc) * 4 + jj];
-        } else {
-          const int h = o - H * D - 4 * H;
-          #pragma unroll 8
-          for (int cc = 0; cc < CR; ++cc) acc += L.a[(base + cc) * kH + h];
-        }
-        out[o] = acc;
-      }
-    }
-    wave_sync();
-    cur = nxt;
-  }
 }
 
 template <int CP, int DM>
@@ -818,7 +629,7 @@ __global__ __launch_bounds__(256) void attn_bwd_wave_kernel(dgppo_gnn_attn_args 
   float* preW = lds;
   float* preb = preW + kD0 * DM;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  CV L(lds + wave_header_floats<DM>() + wave * wfloats, CR, gpw * n * DM, true);
+  CV L(lds + wave_header_floats<DM>() + wave * wfloats, CR);
   const int W = H * (D + 5);
   const int slot = lane / CP, c = lane % CP;
   const int lr = slot * CR + c;
@@ -997,12 +808,6 @@ __global__ __launch_bounds__(256) void attn_bwd_wave_kernel(dgppo_gnn_attn_args 
   }
 }
 
-int pick_cp(int C) {
-  int cp = 8;
-  while (cp < C) cp <<= 1;
-  return cp;
-}
-
 // ================================================================================================
 // Forward, row-block form (C <= 32, H = 3, D <= 32, sender table given): a 256-thread workgroup
 // takes 16 consecutive receiver rows, each wave two rows per sub-round (32 lanes = candidates) for
@@ -1013,18 +818,8 @@ int pick_cp(int C) {
 // ================================================================================================
 namespace fwd2 {
 constexpr int kSR = 2, kQP = 100;
-// xs row pitch: x (DM floats; the pre-transform writes 32) then the edge features at column EC
-template <int DM>
-struct Pitch {
-  // XSP = EC + 4 (12 / 20 / 36 floats): every 16 consecutive lanes' row starts fall on distinct 4-bank groups,
-  // so the per-lane float4 row reads and the pre-transform's strided accesses are bank-conflict free (a 40-float
-  // pitch put lanes L and L + 8 on the same banks)
-  static constexpr int EC = DM <= 8 ? 8 : (DM <= 16 ? 16 : 32), XSP = EC + 4, AW = 64 * (XSP + 4);
-};
-template <int DM>
-constexpr size_t lds_floats() {
-  return (size_t)kRows * kQP + kD0 * 32 + 32 + 4 * Pitch<DM>::AW;
-}
+// LDS: the block's [qt | beta] rows, pre_W and pre_b (every instantiation)
+constexpr size_t lds_floats() { return (size_t)kRows * kQP + kD0 * 32 + 32; }
 }  // namespace fwd2
 
 // Register form of the row-block forward (round 6: the LDS-staged form it replaced is removed): each lane's pair row x stays in registers (pre mode: relu(x_raw pre_W + pre_b) by VALU
@@ -1145,25 +940,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   }
 }
 
-bool fwd2_ok(const dgppo_gnn_attn_args* p) {
-  static const bool off = [] {
-    const char* e = getenv("DGPPO_ATTN_FWD1");
-    return e && atoi(e) != 0;
-  }();
-  return !off && p->H == kH && p->C <= 32 && p->D <= 32 && p->F <= 64 && p->sidx != nullptr &&
-         (int64_t)p->G * p->n_agents < (int64_t)1 << 30 && (p->xa == nullptr || p->D0 <= kD0);
-}
-
-void fwd2_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
-  const int64_t rows = (int64_t)p->G * p->n_agents;
-  const unsigned grid = (unsigned)((rows + kRows - 1) / kRows);
-  const bool no_pre = !(p->xa && p->pre_W);
-  const size_t bytes = ((size_t)kRows * fwd2::kQP + kD0 * 32 + 32) * sizeof(float);
-  if (p->D <= 8 && no_pre) hipLaunchKernelGGL(attn_fwd2r_kernel<8>, dim3(grid), dim3(256), bytes, s, *p);
-  else if (p->D <= 16 && no_pre) hipLaunchKernelGGL(attn_fwd2r_kernel<16>, dim3(grid), dim3(256), bytes, s, *p);  // e.g. Omni's 10-wide first layer
-  else hipLaunchKernelGGL(attn_fwd2r_kernel<32>, dim3(grid), dim3(256), bytes, s, *p);
-}
-
 // ================================================================================================
 // Backward, row-block form (same scope as the row-block forward; agent mode, or full mode without
 // dx).  A persistent workgroup walks blocks of (16 / n) whole graphs; each wave two rows per
@@ -1176,18 +952,13 @@ void fwd2_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
 // into one partial row per workgroup.  Deterministic: no atomics.
 // ================================================================================================
 namespace bwd2 {
-constexpr int kSR = 2, kMaxBlocks = 1024;
+constexpr int kSR = 2;
 // per-head stride HS of the qt / dxbar rows, row pitches, xs pitch (x | x_raw | 1 in pre mode)
 template <int DM>
 struct Lay {
   static constexpr int HS = DM <= 8 ? 8 : (DM <= 16 ? 16 : 32), QP = 3 * HS + 4, GP = 3 * HS + 16;
   static constexpr int XSP = DM <= 8 ? 12 : (DM <= 16 ? 20 : 44), AW = 64 * (XSP + 4);
 };
-template <int DM>
-size_t lds_floats(int n, int D) {
-  using L = Lay<DM>;
-  return (size_t)kRows * (L::QP + L::GP) + kD0 * 32 + 32 + 4 * L::AW + (size_t)kRows * n * D;
-}
 }  // namespace bwd2
 
 // Register form of the row-block backward (round 6: the LDS-staged form it replaced is removed): a
@@ -1498,145 +1269,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   }
 }
 
-bool bwd2_ok(const dgppo_gnn_attn_args* p) {
-  static const bool off = [] {
-    const char* e = getenv("DGPPO_ATTN_BWD1");
-    return e && atoi(e) != 0;
-  }();
-  if (off || p->H != kH || p->C > 32 || p->D > 32 || p->F > 64 || !p->sidx || p->n_agents > kRows) return false;
-  if (p->xa == nullptr) return p->dx == nullptr && p->D <= 32;
-  if (p->D0 > kD0) return false;
-  if (p->pre_W && p->D > 32) return false;
-  return bwd2r::lds_floats<32>(p->n_agents, p->D) * sizeof(float) <= 160 * 1024;
-}
-
-int64_t bwd2_grid(const dgppo_gnn_attn_args* p, int64_t* nblk) {
-  // persistent-grid cap: the resident workgroups, 3 per CU for the DM = 32 instantiation (47.7 KB of LDS, 3 waves per
-  // SIMD), 6 per CU for the narrower ones (512 / 2048 / 4096 measured no different)
-  const bool wide = p->D > 16 || (p->xa && p->pre_W);  // the DM = 32 instantiation
-  const int64_t cap = wide ? 768 : 1536;
-  const int gpb = kRows / p->n_agents;
-  *nblk = (p->G + gpb - 1) / gpb;
-  return *nblk < cap ? *nblk : cap;
-}
-
-void bwd2_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
-  int64_t nblk;
-  const unsigned grid = (unsigned)bwd2_grid(p, &nblk);
-  const bool no_pre = !(p->xa && p->pre_W);
-  const int v = p->D <= 8 && no_pre ? 0 : (p->D <= 16 && no_pre ? 1 : 2);  // DM 8 / 16 / 32
-  const size_t bytes = (v == 0   ? bwd2r::lds_floats<8>(p->n_agents, p->D)
-                        : v == 1 ? bwd2r::lds_floats<16>(p->n_agents, p->D)
-                                 : bwd2r::lds_floats<32>(p->n_agents, p->D)) *
-                       sizeof(float);
-  const void* fn = v == 0 ? (const void*)attn_bwd2r_kernel<8>
-                          : (v == 1 ? (const void*)attn_bwd2r_kernel<16> : (const void*)attn_bwd2r_kernel<32>);
-  if (bytes > 64 * 1024) allow_lds(fn);
-  hipLaunchKernelGGL(reinterpret_cast<void (*)(dgppo_gnn_attn_args, int64_t)>(const_cast<void*>(fn)), dim3(grid),
-                     dim3(256), bytes, s, *p, nblk);
-}
-
-struct Plan {
-  int cp, dm, gpb;
-  int64_t nblk, grid;
-  size_t bytes;
-  bool wave;
-  int wfloats;
-};
-
-template <int CP, int DM>
-Plan plan_t(const dgppo_gnn_attn_args* p, bool bwd) {
-  constexpr int R = 256 / CP;
-  Plan pl{CP, DM, 1, 0, 0, 0, false, 0};
-  const bool full_dx = bwd && p->xa == nullptr && p->dx != nullptr;
-  // measured on MI355X (LidarSpread n8, 16384 graphs): the block-synchronous forward and the
-  // wave-independent backward are the faster pair; DGPPO_ATTN_WAVE=0/1 forces either family
-  static const int wave_env = [] {
-    const char* e = getenv("DGPPO_ATTN_WAVE");
-    return e ? atoi(e) : -1;
-  }();
-  const bool use_wave = wave_env < 0 ? bwd : wave_env != 0;
-  if (CP <= 64 && !full_dx && use_wave) {  // wave-independent kernels
-    constexpr int RW = 64 / CP;
-    pl.wave = true;
-    pl.gpb = RW >= p->n_agents ? RW / p->n_agents : 1;  // graphs per wave item
-    const int cbf = bwd ? pl.gpb * p->n_agents * DM : 0;
-    pl.wfloats = (int)WaveCarve<CP, DM>::floats(cand_rows(p->C, CP), cbf, bwd);
-    size_t tot = wave_header_floats<DM>() + 4 * (size_t)pl.wfloats;
-    if (bwd && tot < (size_t)wave_header_floats<DM>() + 32 * (32 * ((DM + 31) / 32) + 1))
-      tot = wave_header_floats<DM>() + 32 * (32 * ((DM + 31) / 32) + 1);
-    pl.bytes = tot * sizeof(float);
-    pl.nblk = (p->G + pl.gpb - 1) / pl.gpb;  // wave items
-    const int64_t blocks = (pl.nblk + 3) / 4;
-    pl.grid = blocks < kMaxBlocks ? blocks : kMaxBlocks;
-    return pl;
-  }
-  const size_t fixed = bwd ? BwdCarve<CP, DM>::floats_fixed(cand_rows(p->C, CP), p->n_agents)
-                           : Carve<CP, DM>::floats_fixed(cand_rows(p->C, CP), false);
-  pl.gpb = R >= p->n_agents ? R / p->n_agents : 1;
-  const bool agent_mode = p->xa != nullptr;
-  const bool dx = bwd && (agent_mode ? p->dxa != nullptr : p->dx != nullptr);
-  const size_t per_graph = dx && !agent_mode ? (size_t)p->N * p->D : 0;
-  while (pl.gpb > 1 && (fixed + pl.gpb * per_graph) * sizeof(float) > 64 * 1024) --pl.gpb;
-  pl.bytes = (fixed + pl.gpb * per_graph) * sizeof(float);
-  pl.nblk = (p->G + pl.gpb - 1) / pl.gpb;
-  pl.grid = pl.nblk < kMaxBlocks ? pl.nblk : kMaxBlocks;
-  return pl;
-}
-
-template <int DM>
-Plan plan_cp(const dgppo_gnn_attn_args* p, bool bwd) {
-  switch (pick_cp(p->C)) {
-    case 8: return plan_t<8, DM>(p, bwd);
-    case 16: return plan_t<16, DM>(p, bwd);
-    case 32: return plan_t<32, DM>(p, bwd);
-    case 64: return plan_t<64, DM>(p, bwd);
-    default: return plan_t<128, DM>(p, bwd);
-  }
-}
-
-Plan make_plan(const dgppo_gnn_attn_args* p, bool bwd) {
-  if (p->D <= 8) return plan_cp<8>(p, bwd);
-  if (p->D <= 32) return plan_cp<32>(p, bwd);
-  return plan_cp<64>(p, bwd);
-}
-
-template <int CP, int DM>
-void launch_t(const dgppo_gnn_attn_args* p, const Plan& pl, bool bwd, hipStream_t s) {
-  if (pl.bytes > 64 * 1024)  // allow up to the CU's 160 KB
-    allow_lds(bwd ? (const void*)attn_bwd_kernel<CP, DM> : (const void*)attn_fwd_kernel<CP, DM>);
-  if (pl.wave) {
-    if constexpr (CP <= 64) {
-      if (pl.bytes > 64 * 1024)
-        allow_lds(bwd ? (const void*)attn_bwd_wave_kernel<CP, DM> : (const void*)attn_fwd_wave_kernel<CP, DM>);
-      if (bwd)
-        hipLaunchKernelGGL((attn_bwd_wave_kernel<CP, DM>), dim3((unsigned)pl.grid), dim3(256), pl.bytes, s, *p,
-                           pl.gpb, pl.nblk, pl.wfloats);
-      else
-        hipLaunchKernelGGL((attn_fwd_wave_kernel<CP, DM>), dim3((unsigned)pl.grid), dim3(256), pl.bytes, s, *p,
-                           pl.gpb, pl.nblk, pl.wfloats);
-    }
-    return;
-  }
-  if (bwd)
-    hipLaunchKernelGGL((attn_bwd_kernel<CP, DM>), dim3((unsigned)pl.grid), dim3(256), pl.bytes, s, *p, pl.gpb,
-                       pl.nblk);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<CP, DM>), dim3((unsigned)pl.grid), dim3(256), pl.bytes, s, *p, pl.gpb,
-                       pl.nblk);
-}
-
-template <int DM>
-void launch_cp(const dgppo_gnn_attn_args* p, const Plan& pl, bool bwd, hipStream_t s) {
-  switch (pl.cp) {
-    case 8: launch_t<8, DM>(p, pl, bwd, s); break;
-    case 16: launch_t<16, DM>(p, pl, bwd, s); break;
-    case 32: launch_t<32, DM>(p, pl, bwd, s); break;
-    case 64: launch_t<64, DM>(p, pl, bwd, s); break;
-    default: launch_t<128, DM>(p, pl, bwd, s); break;
-  }
-}
-
 // ================================================================================================
 // Forward, graph form, for candidate rows wider than the row-block kernels' 32 (dense graphs, e.g.
 // LidarSpread n = 32: 32 agent + 32 goal + 8 hit candidates per agent).  One workgroup per graph:
@@ -1659,19 +1291,12 @@ constexpr int row_pitch() { return DM == 32 ? 36 : DM + 1; }
 // staged; a receiver's own hit rows -- used by that receiver alone -- are computed by the lane that attends over
 // them (relu(x_raw W4 + b4), the staging's order of operations) into the wave's slots.  LidarSpread n = 32: 75 KB
 // -> 37 KB of LDS per graph, 2 -> 4 resident graphs per CU.
-struct Plan {
-  int ns, cp, slots;
-};
 template <int DM>
-size_t wave_floats(const Plan& pl) {
-  return (size_t)pl.cp * (kH + 1 + 4) + (size_t)pl.slots * row_pitch<DM>();
-}
-template <int DM>
-size_t lds_floats(int n, const Plan& pl) {
-  const size_t w = 4 * wave_floats<DM>(pl);
-  const size_t pw = (size_t)kD0 * DM + DM;                           // pre weights | bias
-  const size_t st = (((size_t)pl.ns * kD0 + 3) & ~(size_t)3) + (pl.slots > 0 ? 0 : pw);  // staging temporaries
-  return (size_t)pl.ns * row_pitch<DM>() + (size_t)n * (kH * DM + 4) + (pl.slots > 0 ? pw : 0) + (w > st ? w : st);
+size_t lds_floats(int n, int ns, int cp, int slots) {
+  const size_t w = 4 * ((size_t)cp * (kH + 1 + 4) + (size_t)slots * row_pitch<DM>());  // the 4 waves' buffers
+  const size_t pw = (size_t)kD0 * DM + DM;                                             // pre weights | bias
+  const size_t st = (((size_t)ns * kD0 + 3) & ~(size_t)3) + (slots > 0 ? 0 : pw);      // staging temporaries
+  return (size_t)ns * row_pitch<DM>() + (size_t)n * (kH * DM + 4) + (slots > 0 ? pw : 0) + (w > st ? w : st);
 }
 }  // namespace gfwd
 
@@ -1692,7 +1317,7 @@ __global__ __launch_bounds__(256) void attn_fwd_graph_kernel(dgppo_gnn_attn_args
   constexpr bool V4 = DM == 32;  // float4 logits / weighted sums (rows zero-padded to DM)
   const int n = p.n_agents, D = p.D, F = p.F, C = p.C, H = kH;
   const int64_t g = blockIdx.x;
-  const bool otf = V4 && slots > 0;       // rows >= ns computed on the fly (gfwd::Plan)
+  const bool otf = V4 && slots > 0;       // rows >= ns computed on the fly (plan())
   float* X = lds;                         // [ns][XP] staged sender rows
   float* Q = X + (size_t)ns * XP;         // [n][QP]: qt_h (DM stride) | beta_h at kH DM + h
   float* PWp = Q + (size_t)n * QP;        // on the fly: the persistent pre weights [D0][D] | b [D]
@@ -2312,133 +1937,212 @@ __global__ __launch_bounds__(512) void attn_bwd_graph32_kernel(dgppo_gnn_attn_ar
   }
 }
 
-bool gbwd32_ok(const dgppo_gnn_attn_args* p) {
-  static const bool off = [] {
-    const char* e = getenv("DGPPO_ATTN_GRAPH");
-    const char* e32 = getenv("DGPPO_ATTN_GBWD32");
-    return (e && atoi(e) == 0) || (e32 && atoi(e32) == 0);
+// ================================================================================================
+// Host dispatch.  plan() is the one place that decides which kernel a call runs and with what grid,
+// LDS size and extra arguments; run() launches from it, dgppo_gnn_attn_partial_blocks (the rows of
+// the backward's dpre_part workspace) is its grid, and dgppo_gnn_attn_plan shows it to callers.
+//
+//   direction  family       taken when (first match; H = 3 and a sender table for all but block / wave)
+//   forward    GRAPH_FWD    32 < C <= 128, D <= 32; one workgroup per graph
+//              FWD2R        C <= 32, D <= 32, F <= 64, G n < 2^30; 16 receiver rows per workgroup
+//              BLOCK        everything else
+//   backward   GRAPH_BWD32  32 < C <= 128, 8 < D <= 32, agent mode with pre_W, no dx; grid min(G, 256)
+//              GRAPH_BWD    32 < C <= 128, D <= 8, full mode, no dx; one workgroup per graph
+//              BWD2R        C <= 32, D <= 32, F <= 64, n <= 16, agent mode or no dx; grid capped at 768
+//                           (DM = 32) or 1536
+//              WAVE         C <= 64, unless full mode asks for dx; grid capped at kMaxBlocks
+//              BLOCK        everything else; grid capped at kMaxBlocks
+// A family whose LDS would pass 160 KB is skipped; block / wave past 160 KB is DGPPO_EINVAL.
+//
+// Environment knobs, read once per process (A/B switches between kept kernels):
+//   DGPPO_ATTN_FWD1=1       forward skips FWD2R
+//   DGPPO_ATTN_BWD1=1       backward skips BWD2R
+//   DGPPO_ATTN_GRAPH=0      no graph-form kernel, forward or backward
+//   DGPPO_ATTN_GRAPH32=0    GRAPH_FWD only for D <= 8
+//   DGPPO_ATTN_GBWD32=0     no GRAPH_BWD32
+//   DGPPO_GBWD32_BLOCKS=k   GRAPH_BWD32's grid cap (default 256)
+//   DGPPO_ATTN_GRAPH_OTF=0  GRAPH_FWD stages every row (dgppo_gnn_set_graph_otf overrides it)
+// ================================================================================================
+struct Knobs {
+  bool fwd1, bwd1, graph_off, graph32_off, gbwd32_off;
+  int gbwd32_blocks, graph_otf;
+};
+
+const Knobs& knobs() {
+  static const Knobs k = [] {
+    auto num = [](const char* name, int unset) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : unset;
+    };
+    return Knobs{num("DGPPO_ATTN_FWD1", 0) != 0,    num("DGPPO_ATTN_BWD1", 0) != 0,
+                 num("DGPPO_ATTN_GRAPH", 1) == 0,   num("DGPPO_ATTN_GRAPH32", 1) == 0,
+                 num("DGPPO_ATTN_GBWD32", 1) == 0,  num("DGPPO_GBWD32_BLOCKS", 0),
+                 num("DGPPO_ATTN_GRAPH_OTF", 1) == 0 ? 0 : 1};
   }();
-  return !off && p->H == kH && p->C > 32 && p->C <= gfwd::kMaxC && p->D > 8 && p->D <= 32 && p->sidx && p->xa &&
-         p->pre_W && p->pre_b && p->D0 <= kD0 && !p->dx && p->N > p->n_agents &&
-         gbwd32::lds_floats(p->N, p->n_agents) * sizeof(float) <= 160 * 1024;
+  return k;
 }
 
-// one resident 512-thread workgroup per CU (the LDS of one graph fills most of a CU)
-int64_t gbwd32_grid(const dgppo_gnn_attn_args* p) {
-  static const int64_t knob = [] {
-    const char* e = getenv("DGPPO_GBWD32_BLOCKS");
-    return e ? (int64_t)atoi(e) : (int64_t)0;
-  }();
-  const int64_t cap = knob > 0 ? knob : 256;
-  return p->G < cap ? p->G : cap;
-}
-
-void gbwd32_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
-  const size_t bytes = gbwd32::lds_floats(p->N, p->n_agents) * sizeof(float);
-  if (bytes > 64 * 1024) allow_lds((const void*)attn_bwd_graph32_kernel);
-  hipLaunchKernelGGL(attn_bwd_graph32_kernel, dim3((unsigned)gbwd32_grid(p)), dim3(512), bytes, s, *p);
-}
-
-size_t gbwd_lds_floats(const dgppo_gnn_attn_args* p) {
-  return (size_t)p->N * (8 + 1) + (size_t)p->n_agents * kH * (p->D + 5) + 4 * (size_t)((p->C + 3) & ~3) * (kH + 1);
-}
-
-bool gbwd_ok(const dgppo_gnn_attn_args* p) {
-  static const bool off = [] {
-    const char* e = getenv("DGPPO_ATTN_GRAPH");
-    return e && atoi(e) == 0;
-  }();
-  return !off && p->H == kH && p->C > 32 && p->C <= gfwd::kMaxC && p->D <= 8 && p->sidx && !p->xa && !p->dx &&
-         gbwd_lds_floats(p) * sizeof(float) <= 160 * 1024;
-}
-
-void gbwd_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
-  const size_t bytes = gbwd_lds_floats(p) * sizeof(float);
-  if (bytes > 64 * 1024) allow_lds((const void*)attn_bwd_graph_kernel<8>);
-  hipLaunchKernelGGL(attn_bwd_graph_kernel<8>, dim3((unsigned)p->G), dim3(256), bytes, s, *p, (p->C + 3) & ~3);
-}
-
-// on-the-fly rows in the graph-form forward: -1 = unset (DGPPO_ATTN_GRAPH_OTF, default 1), else 0 / 1
+// on-the-fly rows in the graph-form forward: -1 = the DGPPO_ATTN_GRAPH_OTF knob, else 0 / 1
 // (dgppo_gnn_set_graph_otf: A/B and the bit-identity test)
 int g_graph_otf = -1;
 
-gfwd::Plan gfwd_plan(const dgppo_gnn_attn_args* p) {
-  // every row staged; per-wave candidate buffers at the call's C rounded to 4 (was kMaxC = 128: at the n = 32 first
-  // layer 31.5 -> 26.6 KB per graph, 5 -> 6 resident graphs per CU)
-  gfwd::Plan pl{p->N, (p->C + 3) & ~3, 0};
-  if (g_graph_otf < 0) {
-    const char* e = getenv("DGPPO_ATTN_GRAPH_OTF");
-    g_graph_otf = (e && atoi(e) == 0) ? 0 : 1;
+struct Plan : dgppo_gnn_attn_plan_info {
+  const void* fn;  // the kernel (allow_lds, launch)
+};
+
+constexpr size_t kLdsMax = 160 * 1024;
+
+// the <8> / <16> / <32> instantiation of the row-block pair: the pre transform writes 32-wide rows
+int dm_2r(const dgppo_gnn_attn_args* p) {
+  const bool no_pre = !(p->xa && p->pre_W);
+  return p->D <= 8 && no_pre ? 8 : (p->D <= 16 && no_pre ? 16 : 32);  // 16: e.g. Omni's 10-wide first layer
+}
+
+// block / wave fallbacks of instantiation <CP, DM>.  Measured on MI355X (LidarSpread n8, 16384 graphs): the
+// block-synchronous forward and the wave-independent backward are the faster pair.
+template <int CP, int DM>
+void plan_fallback(const dgppo_gnn_attn_args* p, bool bwd, Plan& pl) {
+  const int n = p->n_agents, CR = cand_rows(p->C, CP);
+  const bool full_dx = bwd && p->xa == nullptr && p->dx != nullptr;
+  pl.cp = CP, pl.dm = DM;
+  if constexpr (CP <= 64) {
+    if (bwd && !full_dx) {
+      constexpr int RW = 64 / CP;
+      constexpr size_t head = wave_header_floats<DM>(), red = 32 * (32 * ((DM + 31) / 32) + 1);
+      pl.family = DGPPO_GNN_ATTN_WAVE;
+      pl.fn = (const void*)attn_bwd_wave_kernel<CP, DM>;
+      pl.gpb = RW >= n ? RW / n : 1;  // graphs per wave item
+      pl.wfloats = (int32_t)WaveCarve<CP, DM>::floats(CR, pl.gpb * n * DM);
+      const size_t waves = 4 * (size_t)pl.wfloats;
+      pl.lds_bytes = (int64_t)((head + (waves > red ? waves : red)) * sizeof(float));
+      pl.nblk = (p->G + pl.gpb - 1) / pl.gpb;  // wave items
+      const int64_t blocks = (pl.nblk + 3) / 4;
+      pl.grid = blocks < kMaxBlocks ? blocks : kMaxBlocks;
+      return;
+    }
   }
-  const int otf = g_graph_otf;
-  const int n = p->n_agents, ns = 2 * n, slots = p->C - ns;
-  // the Spread layout only: N = 2n + n k + 1 nodes and C = 2n + k candidates (every agent, every goal, the
-  // receiver's own k hits), so a receiver has at most C - 2n candidates past the staged rows
-  const bool spread_layout = n > 0 && p->N > ns + 1 && (p->N - 1 - ns) % n == 0 && p->C == ns + (p->N - 1 - ns) / n;
-  if (otf && spread_layout && p->D > 8 && (p->D & 3) == 0 && p->xa && p->pre_W && p->D0 <= kD0 && slots >= 1 &&
-      slots <= gfwd::kMaxSlots)
-    pl = gfwd::Plan{ns, (p->C + 3) & ~3, slots};
+  constexpr int R = 256 / CP;
+  pl.family = DGPPO_GNN_ATTN_BLOCK;
+  pl.fn = bwd ? (const void*)attn_bwd_kernel<CP, DM> : (const void*)attn_fwd_kernel<CP, DM>;
+  const size_t fixed = bwd ? BwdCarve<CP, DM>::floats_fixed(CR, n) : Carve<CP, DM>::floats_fixed(CR, false);
+  const size_t per_graph = full_dx ? (size_t)p->N * p->D : 0;  // the graphs' dx image
+  pl.gpb = R >= n ? R / n : 1;
+  while (pl.gpb > 1 && (fixed + pl.gpb * per_graph) * sizeof(float) > 64 * 1024) --pl.gpb;
+  pl.lds_bytes = (int64_t)((fixed + pl.gpb * per_graph) * sizeof(float));
+  pl.nblk = (p->G + pl.gpb - 1) / pl.gpb;
+  pl.grid = pl.nblk < kMaxBlocks ? pl.nblk : kMaxBlocks;
+}
+
+template <int DM>
+void plan_fallback_cp(const dgppo_gnn_attn_args* p, bool bwd, Plan& pl) {
+  if (p->C <= 8) plan_fallback<8, DM>(p, bwd, pl);
+  else if (p->C <= 16) plan_fallback<16, DM>(p, bwd, pl);
+  else if (p->C <= 32) plan_fallback<32, DM>(p, bwd, pl);
+  else if (p->C <= 64) plan_fallback<64, DM>(p, bwd, pl);
+  else plan_fallback<128, DM>(p, bwd, pl);
+}
+
+// p must be valid().  family DGPPO_GNN_ATTN_NONE: no kernel covers the call (DGPPO_EINVAL).
+Plan plan(const dgppo_gnn_attn_args* p, bool bwd) {
+  const Knobs& k = knobs();
+  const int n = p->n_agents, N = p->N, D = p->D, C = p->C;
+  const bool agent = p->xa != nullptr, pre = agent && p->pre_W != nullptr;
+  const bool tuned = p->H == kH && p->sidx != nullptr && D <= 32 && (!agent || p->D0 <= kD0);
+  const bool graph = tuned && !k.graph_off && C > 32 && C <= gfwd::kMaxC;
+  const bool rows = tuned && C <= 32 && p->F <= 64;
+  Plan pl{};
+  pl.threads = 256;
+  auto take = [&](int family, int dm, const void* fn, int64_t grid, int64_t nblk, size_t floats) {
+    pl.family = family, pl.dm = dm, pl.fn = fn, pl.grid = grid, pl.nblk = nblk;
+    pl.lds_bytes = (int64_t)(floats * sizeof(float));
+    return pl;
+  };
+  if (!bwd && graph && !(D > 8 && k.graph32_off)) {
+    // every row staged, per-wave candidate buffers at the call's C rounded to 4; or, on the Spread layout (N =
+    // 2n + n k + 1 nodes, C = 2n + k candidates: every agent, every goal, the receiver's own k hits) in agent
+    // mode with the pre transform, only the 2n shared rows staged and the receiver's own rows on the fly
+    pl.ns = N, pl.cp = (C + 3) & ~3, pl.slots = 0;
+    const int ns = 2 * n, slots = C - ns;
+    const bool spread_layout = N > ns + 1 && (N - 1 - ns) % n == 0 && C == ns + (N - 1 - ns) / n;
+    if ((g_graph_otf < 0 ? k.graph_otf : g_graph_otf) && spread_layout && D > 8 && (D & 3) == 0 && pre &&
+        slots >= 1 && slots <= gfwd::kMaxSlots)
+      pl.ns = ns, pl.slots = slots;
+    const size_t floats = D <= 8 ? gfwd::lds_floats<8>(n, pl.ns, pl.cp, pl.slots)
+                                 : gfwd::lds_floats<32>(n, pl.ns, pl.cp, pl.slots);
+    if (floats * sizeof(float) <= kLdsMax)
+      return D <= 8 ? take(DGPPO_GNN_ATTN_GRAPH_FWD, 8, (const void*)attn_fwd_graph_kernel<8>, p->G, p->G, floats)
+                    : take(DGPPO_GNN_ATTN_GRAPH_FWD, 32, (const void*)attn_fwd_graph_kernel<32>, p->G, p->G, floats);
+    pl.ns = pl.cp = pl.slots = 0;
+  }
+  if (!bwd && rows && !k.fwd1 && (int64_t)p->G * n < (int64_t)1 << 30) {
+    const int dm = dm_2r(p);
+    const void* fn = dm == 8 ? (const void*)attn_fwd2r_kernel<8>
+                             : (dm == 16 ? (const void*)attn_fwd2r_kernel<16> : (const void*)attn_fwd2r_kernel<32>);
+    const int64_t nblk = ((int64_t)p->G * n + kRows - 1) / kRows;
+    return take(DGPPO_GNN_ATTN_FWD2R, dm, fn, nblk, nblk, fwd2::lds_floats());
+  }
+  if (bwd && graph && !k.gbwd32_off && D > 8 && pre && p->pre_b && !p->dx && N > n) {
+    // one resident 512-thread workgroup per CU (the LDS of one graph fills most of a CU)
+    const size_t floats = gbwd32::lds_floats(N, n);
+    const int64_t cap = k.gbwd32_blocks > 0 ? k.gbwd32_blocks : 256;
+    if (floats * sizeof(float) <= kLdsMax) {
+      pl.threads = 512;
+      return take(DGPPO_GNN_ATTN_GRAPH_BWD32, 32, (const void*)attn_bwd_graph32_kernel, p->G < cap ? p->G : cap, p->G,
+                  floats);
+    }
+  }
+  if (bwd && graph && D <= 8 && !agent && !p->dx) {
+    const int cp = (C + 3) & ~3;
+    const size_t floats = (size_t)N * (8 + 1) + (size_t)n * kH * (D + 5) + 4 * (size_t)cp * (kH + 1);
+    if (floats * sizeof(float) <= kLdsMax) {
+      pl.cp = cp;
+      return take(DGPPO_GNN_ATTN_GRAPH_BWD, 8, (const void*)attn_bwd_graph_kernel<8>, p->G, p->G, floats);
+    }
+  }
+  // the DM = 32 size bounds every instantiation's LDS
+  if (bwd && rows && !k.bwd1 && n <= kRows &&
+      (agent ? bwd2r::lds_floats<32>(n, D) * sizeof(float) <= kLdsMax : !p->dx)) {
+    const int dm = dm_2r(p);
+    const void* fn = dm == 8 ? (const void*)attn_bwd2r_kernel<8>
+                             : (dm == 16 ? (const void*)attn_bwd2r_kernel<16> : (const void*)attn_bwd2r_kernel<32>);
+    const size_t floats = dm == 8 ? bwd2r::lds_floats<8>(n, D)
+                                  : (dm == 16 ? bwd2r::lds_floats<16>(n, D) : bwd2r::lds_floats<32>(n, D));
+    // persistent-grid cap: the resident workgroups, 3 per CU for the DM = 32 instantiation (47.7 KB of LDS, 3 waves
+    // per SIMD), 6 per CU for the narrower ones (512 / 2048 / 4096 measured no different)
+    const int64_t cap = dm == 32 ? 768 : 1536;
+    pl.gpb = kRows / n;
+    const int64_t nblk = (p->G + pl.gpb - 1) / pl.gpb;
+    return take(DGPPO_GNN_ATTN_BWD2R, dm, fn, nblk < cap ? nblk : cap, nblk, floats);
+  }
+  if (D <= 8) plan_fallback_cp<8>(p, bwd, pl);
+  else if (D <= 32) plan_fallback_cp<32>(p, bwd, pl);
+  else plan_fallback_cp<64>(p, bwd, pl);
+  if ((size_t)pl.lds_bytes > kLdsMax) {
+    pl = Plan{};
+    pl.family = DGPPO_GNN_ATTN_NONE;
+  }
   return pl;
 }
 
-size_t gfwd_bytes(const dgppo_gnn_attn_args* p, const gfwd::Plan& pl) {
-  return (p->D <= 8 ? gfwd::lds_floats<8>(p->n_agents, pl) : gfwd::lds_floats<32>(p->n_agents, pl)) * sizeof(float);
-}
-
-bool gfwd_ok(const dgppo_gnn_attn_args* p) {
-  static const bool off = [] {
-    const char* e = getenv("DGPPO_ATTN_GRAPH");
-    return e && atoi(e) == 0;
-  }();
-  // measured (LidarSpread n = 32): 1.6 ms vs 3.1 ms for the block kernel at D <= 8; at D = 32 the float4 form
-  // (DGPPO_ATTN_GRAPH32=0 keeps the block kernel there)
-  static const bool off32 = [] {
-    const char* e = getenv("DGPPO_ATTN_GRAPH32");
-    return e && atoi(e) == 0;
-  }();
-  if (off || p->H != kH || p->C <= 32 || p->C > gfwd::kMaxC || p->D > 32 || !p->sidx) return false;
-  if (p->D > 8 && off32) return false;
-  if (p->xa && p->D0 > kD0) return false;
-  return gfwd_bytes(p, gfwd_plan(p)) <= 160 * 1024;
-}
-
-void gfwd_launch(const dgppo_gnn_attn_args* p, hipStream_t s) {
-  const bool d8 = p->D <= 8;
-  const gfwd::Plan pl = gfwd_plan(p);
-  const size_t bytes = gfwd_bytes(p, pl);
-  if (bytes > 64 * 1024) allow_lds(d8 ? (const void*)attn_fwd_graph_kernel<8> : (const void*)attn_fwd_graph_kernel<32>);
-  if (d8)
-    hipLaunchKernelGGL(attn_fwd_graph_kernel<8>, dim3((unsigned)p->G), dim3(256), bytes, s, *p, pl.ns, pl.cp, pl.slots);
-  else
-    hipLaunchKernelGGL(attn_fwd_graph_kernel<32>, dim3((unsigned)p->G), dim3(256), bytes, s, *p, pl.ns, pl.cp, pl.slots);
+template <class... A>
+void launch(const Plan& pl, hipStream_t s, A... a) {
+  hipLaunchKernelGGL(reinterpret_cast<void (*)(A...)>(const_cast<void*>(pl.fn)), dim3((unsigned)pl.grid),
+                     dim3((unsigned)pl.threads), (size_t)pl.lds_bytes, s, a...);
 }
 
 int run(const dgppo_gnn_attn_args* p, bool bwd, hipStream_t s) {
-  if (!bwd && gfwd_ok(p)) {
-    if (p->G > 0) gfwd_launch(p, s);
-    return 0;
+  const Plan pl = plan(p, bwd);
+  if (pl.family == DGPPO_GNN_ATTN_NONE) return DGPPO_EINVAL;
+  if (pl.lds_bytes > 64 * 1024) allow_lds(pl.fn);  // up to the CU's 160 KB
+  switch (pl.family) {
+    case DGPPO_GNN_ATTN_FWD2R:
+    case DGPPO_GNN_ATTN_GRAPH_BWD32: launch(pl, s, *p); break;
+    case DGPPO_GNN_ATTN_BWD2R: launch(pl, s, *p, pl.nblk); break;
+    case DGPPO_GNN_ATTN_GRAPH_FWD: launch(pl, s, *p, (int)pl.ns, (int)pl.cp, (int)pl.slots); break;
+    case DGPPO_GNN_ATTN_GRAPH_BWD: launch(pl, s, *p, (int)pl.cp); break;
+    case DGPPO_GNN_ATTN_BLOCK: launch(pl, s, *p, (int)pl.gpb, pl.nblk); break;
+    case DGPPO_GNN_ATTN_WAVE: launch(pl, s, *p, (int)pl.gpb, pl.nblk, (int)pl.wfloats); break;
   }
-  if (!bwd && fwd2_ok(p)) {
-    if (p->G > 0) fwd2_launch(p, s);
-    return 0;
-  }
-  if (bwd && gbwd32_ok(p)) {
-    if (p->G > 0) gbwd32_launch(p, s);
-    return 0;
-  }
-  if (bwd && gbwd_ok(p)) {
-    if (p->G > 0) gbwd_launch(p, s);
-    return 0;
-  }
-  if (bwd && bwd2_ok(p)) {
-    if (p->G > 0) bwd2_launch(p, s);
-    return 0;
-  }
-  const Plan pl = make_plan(p, bwd);
-  if (pl.bytes > 160 * 1024) return DGPPO_EINVAL;
-  if (pl.dm == 8) launch_cp<8>(p, pl, bwd, s);
-  else if (pl.dm == 32) launch_cp<32>(p, pl, bwd, s);
-  else launch_cp<64>(p, pl, bwd, s);
   return 0;
 }
 
@@ -2471,14 +2175,17 @@ extern "C" int dgppo_gnn_sender_table(int32_t G, int32_t n_agents, int32_t C, in
   return (int)hipGetLastError();
 }
 
+extern "C" int dgppo_gnn_attn_plan(const dgppo_gnn_attn_args* p, int32_t bwd, dgppo_gnn_attn_plan_info* out) {
+  if (!out) return DGPPO_EINVAL;
+  *out = dgppo_gnn_attn_plan_info{};
+  out->family = DGPPO_GNN_ATTN_NONE;
+  if (!dgppo::valid(p)) return DGPPO_EINVAL;
+  *out = dgppo::plan(p, bwd != 0);
+  return out->family == DGPPO_GNN_ATTN_NONE ? DGPPO_EINVAL : 0;
+}
+
 extern "C" int64_t dgppo_gnn_attn_partial_blocks(const dgppo_gnn_attn_args* p) {
-  if (!dgppo::valid(p)) return 0;
-  if (dgppo::gbwd32_ok(p)) return dgppo::gbwd32_grid(p);
-  if (dgppo::bwd2_ok(p)) {
-    int64_t nblk;
-    return dgppo::bwd2_grid(p, &nblk);
-  }
-  return dgppo::make_plan(p, true).grid;
+  return dgppo::valid(p) ? dgppo::plan(p, true).grid : 0;
 }
 
 extern "C" int dgppo_gnn_set_graph_otf(int32_t on) {

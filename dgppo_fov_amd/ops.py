@@ -362,6 +362,18 @@ def gnn_attn_partial_blocks(dims, cand, receivers, senders, sidx, x, x_gstride, 
     return int(_lib.load().dgppo_gnn_attn_partial_blocks(ctypes.byref(a)))
 
 
+def gnn_attn_plan(bwd: bool, dx=None, dxa=None, **args) -> _lib.GnnAttnPlan:
+    """The kernel family, instantiation, grid and LDS bytes gnn_attn_fwd (bwd False) / gnn_attn_bwd (bwd True) take
+    for `args`, the dict of GraphTransformer._attn_args, with dx / dxa as the backward call passes them (host query,
+    needs no GPU).  ValueError where the call itself would be refused for its shape."""
+    a = _attn_struct(**args)
+    a.dx, a.dxa = _p(dx), _p(dxa)
+    pl = _lib.GnnAttnPlan()
+    _lib.check(_lib.load().dgppo_gnn_attn_plan(ctypes.byref(a), int(bool(bwd)), ctypes.byref(pl)),
+               "dgppo_gnn_attn_plan")
+    return pl
+
+
 # ---- one GraphTransformer layer forward as one kernel (ABI 11) -------------------------------------------
 TAIL_FIELDS = ("W0", "b0", "ln0_s", "ln0_b", "W1", "b1", "ln1_s", "ln1_b", "Wi", "bi", "Wh", "bhn", "Wo", "bo")
 

@@ -388,6 +388,34 @@ typedef struct dgppo_gnn_attn_args {
   int64_t qt_ld, dqt_ld, dbeta_ld;
 } dgppo_gnn_attn_args;
 
+/* The host decisions of a dgppo_gnn_attn_fwd (bwd = 0) / _bwd (bwd != 0) call, without launching anything (needs
+ * no GPU): both launch from this struct.  Returns DGPPO_EINVAL exactly where they would for reasons of shape (the
+ * output pointers attn / xcat / dxcat / dqt / dbeta are not required; family is then NONE), else 0.  dx and dxa
+ * take part in the choice, so pass them as the call will.  The DGPPO_ATTN_* environment knobs (csrc/attn.hip) are
+ * read once per process.  Fields of another family are 0. */
+#define DGPPO_GNN_ATTN_NONE (-1)
+#define DGPPO_GNN_ATTN_FWD2R 0       /* row-block forward: 16 receiver rows per workgroup */
+#define DGPPO_GNN_ATTN_BWD2R 1       /* row-block backward: 16 / n graphs per block, persistent */
+#define DGPPO_GNN_ATTN_GRAPH_FWD 2   /* graph-form forward: one workgroup per graph (C > 32) */
+#define DGPPO_GNN_ATTN_GRAPH_BWD 3   /* graph-form backward, D <= 8 full mode */
+#define DGPPO_GNN_ATTN_GRAPH_BWD32 4 /* graph-form backward, D <= 32 agent mode with pre_W, 512 threads */
+#define DGPPO_GNN_ATTN_BLOCK 5       /* block fallback, forward or backward */
+#define DGPPO_GNN_ATTN_WAVE 6        /* wave-independent fallback, backward */
+typedef struct dgppo_gnn_attn_plan_info {
+  int32_t family;         /* DGPPO_GNN_ATTN_* */
+  int32_t dm;             /* template instantiation: sender-row width DM */
+  int32_t cp;             /* block / wave: template CP (lanes per receiver); graph forms: per-wave candidate pitch */
+  int32_t gpb;            /* block / 2r backward: graphs per block; wave: graphs per wave item */
+  int32_t wfloats;        /* wave: LDS floats per wave */
+  int32_t ns, slots;      /* graph forward: rows staged in LDS, per-wave rows computed on the fly */
+  int32_t threads;        /* workgroup size */
+  int64_t grid;           /* workgroups; the backward writes this many dpre_part rows */
+  int64_t nblk;           /* work items the grid strides over (blocks of gpb graphs, wave items, 16-row blocks) */
+  int64_t lds_bytes;      /* dynamic LDS of the launch */
+} dgppo_gnn_attn_plan_info;
+int dgppo_gnn_attn_plan(const dgppo_gnn_attn_args* args, int32_t bwd, dgppo_gnn_attn_plan_info* out);
+/* Rows of the dpre_part workspace dgppo_gnn_attn_bwd(args) writes: its plan's grid (0 where it returns
+ * DGPPO_EINVAL).  dx takes part in the choice of kernel, so pass it as the call will (agent mode never has one). */
 int64_t dgppo_gnn_attn_partial_blocks(const dgppo_gnn_attn_args* args);
 /* ABI 10, tuning / testing hook: 1 (default) = the graph-form forward computes each receiver's own
  * never-receiver rows on the fly (Lidar layout, D = 32 agent mode with pre_W: only agent and goal rows staged

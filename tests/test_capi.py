@@ -55,6 +55,7 @@ def _c_layout(struct, fields):
                                             (_lib.GemmArgs, "dgppo_gemm_args"),
                                             (_lib.GemmPlan, "dgppo_gemm_plan_info"),
                                             (_lib.GnnAttnArgs, "dgppo_gnn_attn_args"),
+                                            (_lib.GnnAttnPlan, "dgppo_gnn_attn_plan_info"),
                                             (_lib.GnnLayerArgs, "dgppo_gnn_layer_args"),
                                             (_lib.GnnValueTail, "dgppo_gnn_value_tail"),
                                             (_lib.TanhNormalArgs, "dgppo_tanh_normal_args"),
