@@ -164,6 +164,24 @@ class EnvRolloutIO(ctypes.Structure):
     ]
 
 
+class EnvRolloutPlan(ctypes.Structure):  # dgppo_env_rollout_plan_info
+    ROUTES = ("NONE", "VMAS", "LIDAR_WAVE", "MPE_WAVE", "BLOCK", "STEP_LOOP")  # DGPPO_ENV_ROUTE_*
+    _fields_ = [(n, ctypes.c_int32) for n in ("route", "wpg", "size_block", "size_na", "size_no", "size_nr", "size_nk",
+                                               "stage", "rebuild", "threads", "step_launches", "pad_")] + \
+               [(n, ctypes.c_int64) for n in ("grid", "lds_bytes")]
+
+    @property
+    def route_name(self) -> str:
+        return self.ROUTES[self.route]
+
+    @property
+    def size_tag(self):
+        """BLOCK: (BLOCK, NA, NO, NR, NK) of the SizeTag chosen, else None."""
+        if self.route_name != "BLOCK":
+            return None
+        return self.size_block, self.size_na, self.size_no, self.size_nr, self.size_nk
+
+
 class GatherField(ctypes.Structure):
     _fields_ = [("src", c_f32p), ("dst", c_f32p), ("row_elems", ctypes.c_int64), ("src_tstride", ctypes.c_int64),
                 ("src_estride", ctypes.c_int64)]
@@ -334,6 +352,9 @@ SIGNATURES = {
     "dgppo_env_reset": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvResetIO), ctypes.c_void_p]),
     "dgppo_env_reset_states": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvResetIO), ctypes.c_void_p]),
     "dgppo_env_rollout": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvRolloutIO), ctypes.c_void_p]),
+    "dgppo_env_rollout_plan": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvRolloutIO),
+                                              ctypes.POINTER(EnvRolloutPlan)]),
+    "dgppo_env_set_rollout_wpg": (ctypes.c_int, [ctypes.c_int]),
     "dgppo_env_get_graph": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphIO), ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),

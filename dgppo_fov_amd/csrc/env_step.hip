@@ -3766,6 +3766,40 @@ __host__ __device__ __forceinline__ dgppo_env_step_io step_io_at(const dgppo_env
   q.cost = r.step.cost + t * r.t_cost;
   return q;
 }
+// One dgppo_env_step launch: the kernel family, workgroup size, grid and dynamic LDS (dgppo_env_step launches from
+// it; dgppo_env_rollout_plan describes its STEP_LOOP route with it).  DGPPO_EINVAL where the step refuses the LDS.
+enum StepKind { STEP_VARIANT, STEP_WAVE, STEP_OMNI, STEP_BLOCK };
+struct StepShape {
+  StepKind kind;
+  int threads;
+  int64_t grid;
+  size_t lds;
+};
+static int step_shape(const dgppo_env_cfg* cfg, const float* edges, int64_t edges_stride, const float* out_states,
+                      int64_t out_states_stride, int64_t n_env, StepShape* sh) {
+  if (cfg->variant != DGPPO_VARIANT_NONE) {
+    *sh = {STEP_VARIANT, var::kT, n_env, var::lds_floats(*cfg) * sizeof(float)};
+    return sh->lds > 64 * 1024 ? DGPPO_EINVAL : 0;
+  }
+  if (wave_config(cfg, edges, edges_stride, 0, out_states, out_states_stride, 0)) {
+    const size_t lds = cfg->state_dim == 4 ? kWaveStepLds<4> : (cfg->state_dim == 5 ? kWaveStepLds<5> : kWaveStepLds<kOmniSD>);
+    *sh = {STEP_WAVE, 256, (int64_t)wave_step_grid(n_env).x, lds};
+    return 0;
+  }
+  if (cfg->engine == DGPPO_ENGINE_OMNI) {
+    *sh = {STEP_OMNI, 256, n_env, omni_step_lds_bytes(*cfg)};
+    return sh->lds > 64 * 1024 ? DGPPO_EINVAL : 0;
+  }
+  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k,
+                 cfg->engine != DGPPO_ENGINE_MPE);
+  int block = 0;
+  auto take = [&](auto z) { block = decltype(z)::BLOCK; };
+  if (cfg->engine == DGPPO_ENGINE_MPE) visit_sizes<DGPPO_ENGINE_MPE>(*cfg, take);
+  else visit_sizes<DGPPO_ENGINE_LIDAR>(*cfg, take);
+  *sh = {STEP_BLOCK, block, n_env, (size_t)cv.total * sizeof(float)};
+  return 0;
+}
+
 extern "C" int dgppo_env_step(const dgppo_env_cfg* cfg, const dgppo_env_step_io* io, void* stream) {
   if (validate(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
   if (vmas::is_vmas(cfg)) return vmas::step(cfg, io, stream);
@@ -3776,22 +3810,20 @@ extern "C" int dgppo_env_step(const dgppo_env_cfg* cfg, const dgppo_env_step_io*
   const bool lidar = cfg->engine != DGPPO_ENGINE_MPE && cfg->n_obs > 0;
   if (lidar && (!io->obstacles || !io->ray_dirs)) return DGPPO_EINVAL;
   const hipStream_t s = (hipStream_t)stream;
-  if (cfg->variant != DGPPO_VARIANT_NONE)
+  StepShape sh;
+  if (step_shape(cfg, io->edges, io->edges_stride, io->out_states, io->out_states_stride, io->n_env, &sh))
+    return DGPPO_EINVAL;
+  if (sh.kind == STEP_VARIANT)
     return var::launch(var::step_kernel<DGPPO_ENGINE_MPE>, var::step_kernel<DGPPO_ENGINE_LIDAR>, *cfg, *io, s);
-  if (wave_config(cfg, io->edges, io->edges_stride, 0, io->out_states, io->out_states_stride, 0)) {
+  if (sh.kind == STEP_WAVE) {
     launch_wave_step(cfg, *io, s);
     return (int)hipGetLastError();
   }
-  if (cfg->engine == DGPPO_ENGINE_OMNI) {
-    const size_t sh = omni_step_lds_bytes(*cfg);
-    if (sh > 64 * 1024) return DGPPO_EINVAL;
-    hipLaunchKernelGGL(omni_step_kernel<256>, dim3((unsigned)io->n_env), dim3(256), sh, s, *cfg, *io);
+  if (sh.kind == STEP_OMNI) {
+    hipLaunchKernelGGL(omni_step_kernel<256>, dim3((unsigned)io->n_env), dim3(256), sh.lds, s, *cfg, *io);
     return (int)hipGetLastError();
   }
-  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k,
-                 cfg->engine != DGPPO_ENGINE_MPE);
-  const size_t shmem = (size_t)cv.total * sizeof(float);
-  dispatch_step(*cfg, *io, shmem, (hipStream_t)stream);
+  dispatch_step(*cfg, *io, sh.lds, s);
   return (int)hipGetLastError();
 }
 
@@ -3809,33 +3841,50 @@ extern "C" int dgppo_env_reset_states(const dgppo_env_cfg* cfg, const dgppo_env_
   return (int)hipGetLastError();
 }
 
-// envs per workgroup of the persistent rollout (DGPPO_ROLLOUT_WPG = 1, 4 or 8 forces it).  Per LidarSpread
+// envs per workgroup of the persistent rollout: 0 = automatic, 1 / 4 / 8 forced; initialised from DGPPO_ROLLOUT_WPG,
+// changed by dgppo_env_set_rollout_wpg (A/B timing and the per-instantiation tests).  Per LidarSpread
 // episode (reset + 128 steps, 4096 envs): 1 env 1.59 ms, 4 envs 1.37, 8 envs 1.34, 16 envs 1.41 (register
 // spills); pooling the ray casts of more envs evens out their item counts between the barriers.  Below 2048
 // envs the grid, not the pooling, sets the pace: LidarBicycleTarget at 512 envs (config 4's 8-GPU share)
 // 8 envs 0.959 ms, 4 envs 0.838, 1 env 0.894 -- so 4 there.
-static int rollout_wpg(int64_t n_env) {
-  static const int forced = [] {
+static int g_rollout_wpg = -1;
+static int rollout_wpg_forced() {
+  if (g_rollout_wpg < 0) {
     const char* e = getenv("DGPPO_ROLLOUT_WPG");
     const int v = e ? atoi(e) : 0;
-    return v == 1 || v == 4 || v == 8 ? v : 0;
-  }();
+    g_rollout_wpg = v == 1 || v == 4 || v == 8 ? v : 0;
+  }
+  return g_rollout_wpg;
+}
+static int rollout_wpg(int64_t n_env) {
+  const int forced = rollout_wpg_forced();
   return forced ? forced : (n_env >= 2048 ? 8 : 4);
 }
 
+extern "C" int dgppo_env_set_rollout_wpg(int wpg) {
+  if (wpg != 0 && wpg != 1 && wpg != 4 && wpg != 8) return DGPPO_EINVAL;
+  const int prev = rollout_wpg_forced();
+  g_rollout_wpg = wpg;
+  return prev;
+}
+
+template <int SD>
+constexpr size_t kRolloutWaveLds = sizeof(float) * (wv::Carve<SD, 3>::total + wv::kRolloutActFloats);  // per env
+
 template <int ENGINE, int GOAL, int SD, int WPG>
-static void launch_rollout_w(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, hipStream_t s) {
-  const size_t sh = WPG * sizeof(float) * (wv::Carve<SD, 3>::total + wv::kRolloutActFloats);
-  hipLaunchKernelGGL((wv::lidar_rollout_wave_kernel<ENGINE, GOAL, SD, 3, WPG>),
-                     dim3((unsigned)((r.step.n_env + WPG - 1) / WPG)), dim3(64 * WPG), sh, s, c, r);
+static void launch_rollout_w(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, const dgppo_env_rollout_plan_info& pl,
+                             hipStream_t s) {
+  hipLaunchKernelGGL((wv::lidar_rollout_wave_kernel<ENGINE, GOAL, SD, 3, WPG>), dim3((unsigned)pl.grid),
+                     dim3((unsigned)pl.threads), (size_t)pl.lds_bytes, s, c, r);
 }
 
 template <int ENGINE, int GOAL, int SD>
-static void launch_rollout(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, hipStream_t s) {
-  const int w = rollout_wpg(r.step.n_env);
-  if (w == 4) launch_rollout_w<ENGINE, GOAL, SD, 4>(c, r, s);
-  else if (w == 8) launch_rollout_w<ENGINE, GOAL, SD, 8>(c, r, s);
-  else launch_rollout_w<ENGINE, GOAL, SD, 1>(c, r, s);
+static void launch_rollout(const dgppo_env_cfg& c, const dgppo_env_rollout_io& r, const dgppo_env_rollout_plan_info& pl,
+                           hipStream_t s) {
+  const int w = pl.wpg;
+  if (w == 4) launch_rollout_w<ENGINE, GOAL, SD, 4>(c, r, pl, s);
+  else if (w == 8) launch_rollout_w<ENGINE, GOAL, SD, 8>(c, r, pl, s);
+  else launch_rollout_w<ENGINE, GOAL, SD, 1>(c, r, pl, s);
 }
 
 #ifdef DGPPO_ENV_STAMPS
@@ -3859,9 +3908,33 @@ extern "C" int dgppo_env_diag_stamps(unsigned long long* out) {
 }
 #endif
 
-extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* r, void* stream) {
+// DGPPO_ENV_BLOCK_ROLLOUT=0: the workgroup-per-env shapes take T step launches instead of one persistent launch
+static bool block_rollout_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("DGPPO_ENV_BLOCK_ROLLOUT");
+    return !(e && atoi(e) == 0);
+  }();
+  return on;
+}
+// DGPPO_MPE_WAVE=0 keeps MPE n = 3 / 3 obstacles on the workgroup-per-env kernel
+static bool mpe_wave_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("DGPPO_MPE_WAVE");
+    return !(e && atoi(e) == 0);
+  }();
+  return on;
+}
+
+// Every host decision of dgppo_env_rollout, in the order it takes them (include/dgppo_hip.h has the route table)
+extern "C" int dgppo_env_rollout_plan(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* r,
+                                      dgppo_env_rollout_plan_info* out) {
+  if (!out) return DGPPO_EINVAL;
+  *out = dgppo_env_rollout_plan_info{};
   if (validate(cfg) || !r || r->T < 0 || r->step.n_env < 0) return DGPPO_EINVAL;
-  if (vmas::is_vmas(cfg)) return vmas::rollout(cfg, r, stream);
+  if (vmas::is_vmas(cfg)) {
+    out->route = DGPPO_ENV_ROUTE_VMAS;
+    return 0;
+  }
   const dgppo_env_step_io& io = r->step;
   if (r->T == 0 && !r->rebuild_first) return 0;
   if (io.n_env == 0) return 0;
@@ -3870,40 +3943,35 @@ extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollo
     return DGPPO_EINVAL;
   const bool lidar = cfg->engine != DGPPO_ENGINE_MPE && cfg->n_obs > 0;
   if (lidar && (!io.obstacles || !io.ray_dirs)) return DGPPO_EINVAL;
-  const hipStream_t s = (hipStream_t)stream;
+  dgppo_env_rollout_plan_info pl{};
   if (wave_config(cfg, io.edges, io.edges_stride, r->t_edges, io.out_states, io.out_states_stride, r->t_states)) {
-    visit_engine_goal(*cfg, [&](auto e) {
-      using E = decltype(e);
-      if constexpr (E::ENGINE != DGPPO_ENGINE_MPE) launch_rollout<E::ENGINE, E::GOAL, E::SD>(*cfg, *r, s);
-    });
-    return (int)hipGetLastError();
+    const int w = rollout_wpg(io.n_env);
+    pl.route = DGPPO_ENV_ROUTE_LIDAR_WAVE;
+    pl.wpg = w;
+    pl.grid = (io.n_env + w - 1) / w;
+    pl.threads = 64 * w;
+    pl.lds_bytes = (int64_t)w * (int64_t)(cfg->state_dim == 4 ? kRolloutWaveLds<4>
+                                          : (cfg->state_dim == 5 ? kRolloutWaveLds<5> : kRolloutWaveLds<kOmniSD>));
+    *out = pl;
+    return 0;
   }
   // other configs: rebuild_first: a states-only reset (dgppo_env_reset_states) left graph 0 unbuilt when the
   // wave kernels took it (a misaligned per-step stride sends the rollout here)
-  if (r->rebuild_first && wave_config(cfg, io.edges, io.edges_stride, 0, io.out_states, io.out_states_stride, 0))
-    launch_rebuild(cfg, io, s);
-  // the workgroup-per-env shapes: one persistent launch for all T steps (DGPPO_ENV_BLOCK_ROLLOUT=0: T launches)
-  static const bool block_rollout = [] {
-    const char* e = getenv("DGPPO_ENV_BLOCK_ROLLOUT");
-    return !(e && atoi(e) == 0);
-  }();
+  pl.rebuild = r->rebuild_first && wave_config(cfg, io.edges, io.edges_stride, 0, io.out_states, io.out_states_stride, 0);
   // MPE n = 3 with 3 obstacles (BASELINE config 2): the wave-per-env persistent rollout (graph 0 is loaded: the MPE
   // reset always builds it); DGPPO_MPE_WAVE=0 or the block step kernels forced keep the workgroup-per-env kernel
-  static const bool mpe_wave = [] {
-    const char* e = getenv("DGPPO_MPE_WAVE");
-    return !(e && atoi(e) == 0);
-  }();
-  if (block_rollout && mpe_wave && r->T > 0 && mpe_wave_config(cfg) &&
+  if (block_rollout_enabled() && mpe_wave_enabled() && r->T > 0 && mpe_wave_config(cfg) &&
       (reinterpret_cast<uintptr_t>(io.edges) % 16u) == 0 && io.edges_stride % 4 == 0 && r->t_edges % 4 == 0) {
-    const size_t sh = 4 * sizeof(float) * wv::mpew::TOTAL;
-    const dim3 grid((unsigned)((io.n_env + 3) / 4));
-    if (cfg->goal_mode == DGPPO_GOAL_SPREAD)
-      hipLaunchKernelGGL((wv::mpew::mpe_rollout_wave_kernel<DGPPO_GOAL_SPREAD>), grid, dim3(256), sh, s, *cfg, *r);
-    else
-      hipLaunchKernelGGL((wv::mpew::mpe_rollout_wave_kernel<DGPPO_GOAL_TARGET>), grid, dim3(256), sh, s, *cfg, *r);
-    return (int)hipGetLastError();
+    pl.route = DGPPO_ENV_ROUTE_MPE_WAVE;
+    pl.wpg = 4;
+    pl.grid = (io.n_env + 3) / 4;
+    pl.threads = 256;
+    pl.lds_bytes = 4 * sizeof(float) * wv::mpew::TOTAL;
+    *out = pl;
+    return 0;
   }
-  if (block_rollout && r->T > 0 && cfg->variant == DGPPO_VARIANT_NONE && cfg->engine != DGPPO_ENGINE_OMNI &&
+  // the workgroup-per-env shapes: one persistent launch for all T steps (DGPPO_ENV_BLOCK_ROLLOUT=0: T launches)
+  if (block_rollout_enabled() && r->T > 0 && cfg->variant == DGPPO_VARIANT_NONE && cfg->engine != DGPPO_ENGINE_OMNI &&
       cfg->n_agents <= 32) {  // (2 n actions per step staged one per thread of a >= 64-thread workgroup)
     const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k,
                    cfg->engine != DGPPO_ENGINE_MPE);
@@ -3913,10 +3981,64 @@ extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollo
     const int64_t act_lds = (act_floats + 3) & ~(int64_t)3;
     const bool stage = act_floats <= kActStage && (cv.total + act_lds) * (int64_t)sizeof(float) <= 64 * 1024;
     const int64_t extra = stage ? act_lds : 0;
-    dispatch_rollout_block(*cfg, *r, (size_t)(cv.total + extra) * sizeof(float), s, stage ? 1 : 0);
+    auto take = [&](auto z) {
+      using Z = decltype(z);
+      pl.size_block = Z::BLOCK, pl.size_na = Z::NA, pl.size_no = Z::NO, pl.size_nr = Z::NR, pl.size_nk = Z::NK;
+    };
+    if (cfg->engine == DGPPO_ENGINE_MPE) visit_sizes<DGPPO_ENGINE_MPE>(*cfg, take);
+    else visit_sizes<DGPPO_ENGINE_LIDAR>(*cfg, take);
+    pl.route = DGPPO_ENV_ROUTE_BLOCK;
+    pl.stage = stage ? 1 : 0;
+    pl.grid = io.n_env;
+    pl.threads = pl.size_block;
+    pl.lds_bytes = (cv.total + extra) * (int64_t)sizeof(float);
+    *out = pl;
+    return 0;
+  }
+  pl.route = DGPPO_ENV_ROUTE_STEP_LOOP;
+  pl.step_launches = r->T;
+  if (r->T > 0) {  // the first step's launch, at the pointers it is given (step 0 writes graph 1)
+    const dgppo_env_step_io q = step_io_at(*r, 0);
+    StepShape sh;
+    if (step_shape(cfg, q.edges, q.edges_stride, q.out_states, q.out_states_stride, q.n_env, &sh))
+      return DGPPO_EINVAL;
+    pl.threads = sh.threads;
+    pl.grid = sh.grid;
+    pl.lds_bytes = (int64_t)sh.lds;
+  }
+  *out = pl;
+  return 0;
+}
+
+extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* r, void* stream) {
+  dgppo_env_rollout_plan_info pl;
+  if (const int rc = dgppo_env_rollout_plan(cfg, r, &pl)) return rc;
+  if (pl.route == DGPPO_ENV_ROUTE_VMAS) return vmas::rollout(cfg, r, stream);
+  if (pl.route == DGPPO_ENV_ROUTE_NONE) return 0;
+  const dgppo_env_step_io& io = r->step;
+  const hipStream_t s = (hipStream_t)stream;
+  if (pl.route == DGPPO_ENV_ROUTE_LIDAR_WAVE) {
+    visit_engine_goal(*cfg, [&](auto e) {
+      using E = decltype(e);
+      if constexpr (E::ENGINE != DGPPO_ENGINE_MPE) launch_rollout<E::ENGINE, E::GOAL, E::SD>(*cfg, *r, pl, s);
+    });
     return (int)hipGetLastError();
   }
-  for (int t = 0; t < r->T; ++t) {
+  if (pl.rebuild) launch_rebuild(cfg, io, s);
+  if (pl.route == DGPPO_ENV_ROUTE_MPE_WAVE) {
+    const dim3 grid((unsigned)pl.grid), block((unsigned)pl.threads);
+    const size_t sh = (size_t)pl.lds_bytes;
+    if (cfg->goal_mode == DGPPO_GOAL_SPREAD)
+      hipLaunchKernelGGL((wv::mpew::mpe_rollout_wave_kernel<DGPPO_GOAL_SPREAD>), grid, block, sh, s, *cfg, *r);
+    else
+      hipLaunchKernelGGL((wv::mpew::mpe_rollout_wave_kernel<DGPPO_GOAL_TARGET>), grid, block, sh, s, *cfg, *r);
+    return (int)hipGetLastError();
+  }
+  if (pl.route == DGPPO_ENV_ROUTE_BLOCK) {
+    dispatch_rollout_block(*cfg, *r, (size_t)pl.lds_bytes, s, pl.stage);
+    return (int)hipGetLastError();
+  }
+  for (int t = 0; t < pl.step_launches; ++t) {
     const dgppo_env_step_io q = step_io_at(*r, t);
     const int rc = dgppo_env_step(cfg, &q, stream);
     if (rc) return rc;

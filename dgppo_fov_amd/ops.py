@@ -177,6 +177,13 @@ def env_rollout(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor], acti
     step t reads graph t and writes graph t+1, reward[t] (T, B), cost[t] (T, B, n, n_cost).
     rebuild_first: graph 0's rows are first built from its agent / goal states (env_reset_states)."""
     _lib.require_gpu(states.device, "dgppo::env_rollout")
+    r = _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost)
+    _lib.check(_lib.load().dgppo_env_rollout(ctypes.byref(env_cfg(cfg)), ctypes.byref(r), _stream(states)),
+               "dgppo_env_rollout")
+
+
+def _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost):
+    """The dgppo_env_rollout_io of env_rollout's tensors (env_rollout and env_rollout_plan both build it here)."""
     T = int(actions.shape[0])
     if states.shape[0] != T + 1 or reward.shape[0] != T or cost.shape[0] != T:
         raise ValueError("env_rollout: graph buffers must hold T+1 graphs, actions / reward / cost T steps")
@@ -200,8 +207,20 @@ def env_rollout(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor], acti
     if receivers.stride(0) != senders.stride(0):
         raise ValueError("env_rollout: receivers and senders need the same time stride")
     r.t_index, r.t_action, r.t_reward, r.t_cost = receivers.stride(0), actions.stride(0), reward.stride(0), cost.stride(0)
-    _lib.check(_lib.load().dgppo_env_rollout(ctypes.byref(env_cfg(cfg)), ctypes.byref(r), _stream(states)),
-               "dgppo_env_rollout")
+    return r
+
+
+def env_rollout_plan(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor], actions: Tensor, ray_dirs: Tensor,
+                     nodes: Tensor, edges: Tensor, states: Tensor, receivers: Tensor, senders: Tensor, reward: Tensor,
+                     cost: Tensor) -> _lib.EnvRolloutPlan:
+    """The route env_rollout would take for these tensors (dgppo_env_rollout_plan: the kernel family, envs per
+    workgroup, block sizes, action staging, grid and LDS), without launching anything.  Tensors on any device: only
+    their addresses' alignment and strides are read."""
+    r = _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost)
+    pl = _lib.EnvRolloutPlan()
+    _lib.check(_lib.load().dgppo_env_rollout_plan(ctypes.byref(env_cfg(cfg)), ctypes.byref(r), ctypes.byref(pl)),
+               "dgppo_env_rollout_plan")
+    return pl
 
 
 @env_rollout.register_fake

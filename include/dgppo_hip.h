@@ -249,7 +249,8 @@ int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_args* a, vo
  * t_cost.  Step t reads graph t and writes graph t+1, reward[t], cost[t]; rebuild_first = 1 first
  * writes graph 0's rows from its agent / goal states and obstacles (after dgppo_env_reset_states).
  * Lidar configs at n = 8, 32 rays, top-8, 3 obstacles run one persistent kernel (a wave per env for
- * all T steps, state in LDS); others loop dgppo_env_step (identical results). */
+ * all T steps, state in LDS); most others a persistent workgroup-per-env kernel, the rest loop dgppo_env_step
+ * (identical results; dgppo_env_rollout_plan below names the route). */
 typedef struct dgppo_env_rollout_io {
   dgppo_env_step_io step;   /* graph 0 in / out (states == out_states), actions / reward / cost of step 0 */
   int32_t T;
@@ -258,6 +259,51 @@ typedef struct dgppo_env_rollout_io {
 } dgppo_env_rollout_io;
 
 int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* io, void* stream);
+
+/* The host decisions of a dgppo_env_rollout(cfg, io) call, without launching anything (no HIP call: needs no GPU);
+ * dgppo_env_rollout launches from this struct.  Pointers are read for NULL and alignment only.  Returns DGPPO_EINVAL
+ * exactly where dgppo_env_rollout would (route is then NONE), else 0.  The routes, in the order they are tried:
+ *   NONE        T == 0 without rebuild_first, or n_env == 0: nothing is launched
+ *   VMAS        the VMAS engines' own rollout (csrc/vmas.hip); nothing else is filled
+ *   LIDAR_WAVE  wave-per-env persistent kernel: Lidar engines, no variant, n = 8, 32 rays, top-8, 3 obstacles, step
+ *               kernel mode auto, edge rows (base, per-env and per-step stride) 16-byte aligned (8-byte for
+ *               LidarOmniTarget) and 4-wide state rows 16-byte aligned; wpg envs per workgroup
+ *   MPE_WAVE    wave-per-env persistent kernel: MPE, no variant, n = 3, 3 obstacles, T > 0, mode auto, edge rows
+ *               16-byte aligned, DGPPO_ENV_BLOCK_ROLLOUT and DGPPO_MPE_WAVE not 0; 4 envs per workgroup
+ *   BLOCK       workgroup-per-env persistent kernel: T > 0, no variant, not LidarOmniTarget, n <= 32,
+ *               DGPPO_ENV_BLOCK_ROLLOUT not 0; size_* name its compile-time sizes (0 / -1: read from cfg), stage = 1
+ *               when the whole episode's actions are staged in LDS
+ *   STEP_LOOP   step_launches calls of dgppo_env_step; threads / grid / lds_bytes describe the first of them (step 0,
+ *               which writes graph 1 at edges + t_edges, out_states + t_states).  They are informational: every
+ *               dgppo_env_step call decides again from its own pointers, so with a per-step stride that breaks the
+ *               wave kernels' alignment later steps can run another step kernel than the first (same results)
+ * rebuild = 1: a launch of the wave step kernel in REBUILD mode builds graph 0 first (rebuild_first set, the config
+ * is the single-step wave kernel's, LIDAR_WAVE was not taken).  The two environment knobs are read once per
+ * process. */
+#define DGPPO_ENV_ROUTE_NONE 0
+#define DGPPO_ENV_ROUTE_VMAS 1
+#define DGPPO_ENV_ROUTE_LIDAR_WAVE 2
+#define DGPPO_ENV_ROUTE_MPE_WAVE 3
+#define DGPPO_ENV_ROUTE_BLOCK 4
+#define DGPPO_ENV_ROUTE_STEP_LOOP 5
+typedef struct dgppo_env_rollout_plan_info {
+  int32_t route;          /* DGPPO_ENV_ROUTE_* */
+  int32_t wpg;            /* envs (waves) per workgroup of the wave routes, else 0 */
+  int32_t size_block, size_na, size_no, size_nr, size_nk; /* BLOCK: the SizeTag<BLOCK, NA, NO, NR, NK> chosen */
+  int32_t stage;          /* BLOCK: actions staged in LDS */
+  int32_t rebuild;        /* a REBUILD launch precedes */
+  int32_t threads;        /* workgroup size of the main launch */
+  int32_t step_launches;  /* STEP_LOOP: dgppo_env_step calls */
+  int32_t pad_;
+  int64_t grid;           /* workgroups of the main launch */
+  int64_t lds_bytes;      /* its dynamic LDS */
+} dgppo_env_rollout_plan_info;
+int dgppo_env_rollout_plan(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* io, dgppo_env_rollout_plan_info* out);
+
+/* Envs per workgroup of the LIDAR_WAVE route (the twin of dgppo_env_set_step_kernel; results are bit-identical):
+ * 0 = automatic (8 from 2048 envs, else 4), 1 / 4 / 8 forced.  Returns the previous value or DGPPO_EINVAL.
+ * Initial value: DGPPO_ROLLOUT_WPG=1|4|8 (default automatic). */
+int dgppo_env_set_rollout_wpg(int wpg);
 
 /* ---- hot path (2): DGPPO update building blocks ------------------------------------------------
  * Batched fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32):

@@ -52,6 +52,8 @@ def _c_layout(struct, fields):
 
 @pytest.mark.parametrize("pystruct,cname", [(_lib.EnvCfg, "dgppo_env_cfg"), (_lib.EnvStepIO, "dgppo_env_step_io"),
                                             (_lib.EnvResetIO, "dgppo_env_reset_io"),
+                                            (_lib.EnvRolloutIO, "dgppo_env_rollout_io"),
+                                            (_lib.EnvRolloutPlan, "dgppo_env_rollout_plan_info"),
                                             (_lib.GemmArgs, "dgppo_gemm_args"),
                                             (_lib.GemmPlan, "dgppo_gemm_plan_info"),
                                             (_lib.GnnAttnArgs, "dgppo_gnn_attn_args"),

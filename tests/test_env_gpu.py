@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from dgppo_fov_amd.env import make_env
+from env_cases import _np, adversarial_lidar_scene, assert_graph_equal, oracle_third  # noqa: F401
 from oracle import env as O
 
 pytestmark = pytest.mark.gpu
@@ -28,26 +29,6 @@ CONFIGS = [
     ("LidarOmniTarget", 4, 0, 8),
 ]
 IDS = [f"{c[0]}-n{c[1]}-o{c[2]}" for c in CONFIGS]
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def assert_graph_equal(g, ref, what=""):
-    for f in ("nodes", "edges", "states"):
-        a, b = _np(getattr(g, f)), ref[f]
-        assert a.shape == b.shape, (what, f, a.shape, b.shape)
-        bad = ~((a == b) | (np.isnan(a) & np.isnan(b)))
-        assert not bad.any(), f"{what} {f}: {bad.sum()} mismatches, first at {np.argwhere(bad)[0]}: {a[bad][:4]} vs {b[bad][:4]}"
-    np.testing.assert_array_equal(_np(g.receivers), ref["receivers"], err_msg=f"{what} receivers")
-    np.testing.assert_array_equal(_np(g.senders), ref["senders"], err_msg=f"{what} senders")
-
-
-def oracle_third(spec, g):
-    if spec.engine == O.ENGINE_MPE:
-        return None
-    return _np(g.env_states.obstacle.packed) if spec.n_obs > 0 else np.zeros((_np(g.states).shape[0], 0, 16), np.float32)
 
 
 @pytest.mark.parametrize("cfg", CONFIGS, ids=IDS)
@@ -240,63 +221,9 @@ def test_env_shards_equal_global_slices(cuda, eid, n, obs):
 
 
 def _adversarial_lidar_inputs(env, spec, B, seed, cuda):
-    """Inputs aimed at the wave kernel's exact ray culling: tiny / huge / ineligible
-    obstacles, edges exactly parallel to a ray, NaN and far-away corners, agents at corners and
-    centres (inside -> alpha 0), agents crowded around one obstacle (> k hits), NaN actions."""
-    rng = np.random.default_rng(seed)
+    """env_cases.adversarial_lidar_scene on the GPU env's own reset arrays, as a graph the step kernels take."""
     g = env.reset(key=seed, n_env=B)
-    states = _np(g.states).copy()
-    ob = _np(g.env_states.obstacle.packed).copy()
-    n = spec.n
-    rays = O.ray_table(spec.n_rays, 0.5)
-    kind = np.arange(B) % 8
-    for b in range(B):
-        k = kind[b]
-        if k == 0:  # random sizes spanning eligibility (rho <= 0.5) and tiny boxes, exact axis angles
-            wh = rng.choice([1e-4, 0.05, 0.3, 0.69, 0.9], size=(3, 2))
-            th = rng.choice([0.0, np.pi / 2, np.pi, rng.uniform(0, 2 * np.pi)], size=3)
-            ob[b] = O.make_rectangles(rng.uniform(0, 1.5, (3, 2)), wh[:, 0], wh[:, 1], th)
-        elif k == 1:  # agents exactly on corners / centres of obstacles
-            for i in range(n):
-                o = i % 3
-                p = ob[b, o, 8 + 2 * (i % 4):10 + 2 * (i % 4)] if i < 4 else ob[b, o, :2]
-                states[b, i, :2] = np.clip(p, 0, 1.5)
-                states[b, i, 2:4] = 0.0
-        elif k == 2:  # obstacle 0 = parallelogram whose first edge is exactly 2 x ray r
-            r = rng.integers(0, spec.n_rays)
-            c = states[b, 0, :2] + rays[(r + 8) % spec.n_rays] * 0.6
-            e1 = rays[r] * np.float32(2.0)
-            e2 = rays[(r + 8) % spec.n_rays] * np.float32(0.5)
-            p0 = c.astype(np.float32)
-            pts = np.stack([p0, p0 - e1, p0 - e1 - e2, p0 - e2]).astype(np.float32)
-            ob[b, 0, 8:] = pts.reshape(-1)
-            ob[b, 0, :2] = pts.mean(0)
-        elif k == 3:  # NaN corner and far / huge obstacles
-            ob[b, 0, 8] = np.nan
-            ob[b, 1, 8:] = ob[b, 1, 8:] + np.float32(1e3)
-            ob[b, 2, 8:] = ob[b, 2, 8:] * np.float32(3.0)
-        elif k == 4:  # everyone crowded around obstacle 0
-            states[b, :n, :2] = ob[b, 0, :2] + rng.uniform(-0.25, 0.25, (n, 2)).astype(np.float32)
-            states[b, :n, :2] = np.clip(states[b, :n, :2], 0, 1.5)
-        elif k == 5:  # agent on the ray line through a corner
-            r = rng.integers(0, spec.n_rays)
-            states[b, 0, :2] = np.clip(ob[b, 1, 8:10] - rays[r] * np.float32(0.5), 0, 1.5)
-            states[b, 0, 2:4] = 0.0
-    a = rng.uniform(-1, 1, (B, n, spec.ad)).astype(np.float32)
-    a[kind == 1] = 0.0
-    a[kind == 5, 0] = 0.0
-    a[6, 0, 0] = np.nan
-    if spec.ad == 3:  # LidarOmniTarget: coincident agents (FoV norm 0), non-unit headings, rates at the
-        # limits, huge / non-finite alpha
-        for b in np.nonzero(kind == 6)[0]:
-            states[b, 1, :2] = states[b, 0, :2]
-            states[b, :n, 2:4] = [0.3, 0.4]
-        for b in np.nonzero(kind == 7)[0]:
-            states[b, :n, 6] = rng.choice([-99.0, 0.0, 99.0], size=n)
-            states[b, :n, 4:6] = rng.choice([-1.9, 2.5], size=(n, 2))
-        a[7, 1, 2] = 1e30
-        a[15, 2, 2] = -np.inf
-        a[23, 3, 2] = np.nan
+    states, ob, a = adversarial_lidar_scene(spec, _np(g.states), _np(g.env_states.obstacle.packed), seed)
     gin = env._assemble(g.nodes, g.edges, torch.from_numpy(states).to(cuda), g.receivers, g.senders,
                         torch.from_numpy(ob).to(cuda))
     return gin, states, ob, a
