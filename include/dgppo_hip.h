@@ -393,6 +393,27 @@ int dgppo_gemm_plan(const dgppo_gemm_args* args, dgppo_gemm_plan_info* out);
  * xcat (G*n, H*(D+5)) = [xbar (H*D) | ebar (H*4) | sig (H)]; bwd consumes dxcat and writes dqt,
  * dq (= dbeta_h * bk_h), dbeta and the sender gradients.
  * cand (n, C): edge ids that may target agent i (checked against receivers at run time).
+ * The candidate table (tests/test_attn_direct_gpu.py holds every kernel family to this on synthetic graphs):
+ *   - candidate (i, c) is VALID when cand[i][c] >= 0 and receivers[g][cand[i][c]] == i; its sender is
+ *     senders[g][cand[i][c]], a node in [0, N).  cand[i][c] == -1 and an edge with another receiver (another agent,
+ *     or the envs' pad N) are masked: weight exactly 0, nothing read through them, no gradient.  Edges that no
+ *     candidate names take no part.
+ *   - a receiver without a valid candidate gets attn and xcat rows of exact zeros, zero dqt / dbeta / dq rows and
+ *     sends no gradient (the fused layer's Y row is then relu(x_i Wu + bu)); one with a single valid candidate gets
+ *     weight exactly 1.
+ *   - slot order and distinctness: the forward (every family, and the fused layer), dqt, dbeta, dq and dpre_part hold
+ *     for ANY slot order and for repeated senders.  The SENDER GRADIENTS dx / dxa need more:
+ *       distinct senders: the valid candidates of one receiver name distinct senders (every backward family: row-block,
+ *         wave, block and the D = 32 graph form keep one image entry per (receiver, sender), and two candidates with one
+ *         sender overwrite or race on it);
+ *       agent j at slot j: in agent mode an agent sender j appears only at slot c == j (slots >= n hold nodes >= n).
+ *         Only the BLOCK backward in agent mode needs this -- the family an agent-mode backward reaches when C > 64
+ *         and GRAPH_BWD32 does not take the call (e.g. H < 3, D > 32 or D <= 8, no sidx, no pre_W, N == n;
+ *         dgppo_gnn_attn_plan names the family); the other families index by sender and take any slot order.
+ *     Every env's agent_candidates table ([agent 0..n-1 | goals | own hits]) satisfies both.
+ *   - the graph-form forward's on-the-fly rows (dgppo_gnn_set_graph_otf, chosen by shape: N = 2n + n k + 1,
+ *     C = 2n + k, k <= 16, D = 32 agent mode with pre_W) take at most k valid senders >= 2n per receiver; a receiver
+ *     with more gets an xcat row of NaN.
  * Sender features, two modes:
  *   full  (xa == NULL): x (G, N, D) holds every node's features; bwd ACCUMULATES dx (G, N, D).
  *   agent (xa != NULL): agent senders (node < n) read xa (G, n, D); other senders are nodes that
