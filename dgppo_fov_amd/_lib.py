@@ -161,6 +161,8 @@ class EnvRolloutIO(ctypes.Structure):
         ("t_states", ctypes.c_int64), ("t_nodes", ctypes.c_int64), ("t_edges", ctypes.c_int64),
         ("t_index", ctypes.c_int64), ("t_action", ctypes.c_int64), ("t_reward", ctypes.c_int64),
         ("t_cost", ctypes.c_int64),
+        ("reset_first", ctypes.c_int32), ("pad_", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("seed_ptr", c_f32p), ("env_offset", ctypes.c_int64),
     ]
 
 
@@ -168,7 +170,8 @@ class EnvRolloutPlan(ctypes.Structure):  # dgppo_env_rollout_plan_info
     ROUTES = ("NONE", "VMAS", "LIDAR_WAVE", "MPE_WAVE", "BLOCK", "STEP_LOOP")  # DGPPO_ENV_ROUTE_*
     _fields_ = [(n, ctypes.c_int32) for n in ("route", "wpg", "size_block", "size_na", "size_no", "size_nr", "size_nk",
                                                "stage", "rebuild", "threads", "step_launches", "pad_")] + \
-               [(n, ctypes.c_int64) for n in ("grid", "lds_bytes")]
+               [(n, ctypes.c_int64) for n in ("grid", "lds_bytes")] + \
+               [(n, ctypes.c_int32) for n in ("reset_launches", "pad2_")]
 
     @property
     def route_name(self) -> str:

@@ -1093,6 +1093,20 @@ constexpr int kOmniSD = 7, kOmniED = 10, kOmniNC = 5;  // LidarOmniTarget state 
 #define DGPPO_ENV_UNI 1
 #endif
 
+// The states-only half of a reset (defined with the reset kernels below): env_reset_kernel runs it behind workgroup
+// barriers, the persistent Lidar rollout (reset_first) one wave per env behind wave-level syncs.
+constexpr int kSampTab = 256;  // candidate pairs drawn ahead of the rejection sampler
+struct BlockSync {
+  __device__ __forceinline__ void operator()() const { __syncthreads(); }
+};
+struct WaveSync {
+  __device__ __forceinline__ void operator()() const;
+};
+template <int ENGINE, int SD, int NTHR, class Sync>
+__device__ __forceinline__ void sample_states(const dgppo_env_cfg& cfg, Rng rng, int tid, int n, int O, Sync sync,
+                                              float* tab, float* pos, float* gl, float* obst, float* nxt, float* goal,
+                                              float* third, uint32_t* count_slot);
+
 namespace wv {
 constexpr int NA = 8, NR = 32, NK = 8;
 constexpr float kCullMargin = 0.01f;
@@ -1990,7 +2004,9 @@ constexpr int kRolloutActFloats = 16 * NA * 3;  // per wave: a 16-step action ch
 // and writes graph t+1's rows into the time-major (T+1, B) buffer, reward[t] and cost[t].  No launch
 // per step, and the 4096 waves drift out of phase, so one wave's store drain overlaps another's compute.
 // rebuild_first: graph 0 is first built from its agent / goal / obstacle rows (after a states-only
-// reset), else its current rows are loaded.
+// reset), else its current rows are loaded.  reset_first: the wave first samples its env itself (the states-only
+// reset: sample_states, one wave per env) and builds graph 0 from the rows it left in LDS -- no reset launch, no
+// kernel boundary, no re-read of the sampled rows; bit-identical to the two launches.
 // (4 waves per SIMD: the whole 4096-env batch resident at once, as for the per-step kernel; without the
 // bound the loop's hoisted addressing takes ~150 VGPRs and a quarter of the workgroups would run after
 // the rest had finished their episodes)
@@ -2002,8 +2018,34 @@ __global__ __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(4))) v
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int wg_items[WPG];
   const dgppo_env_step_io& g0 = r.step;
-  if (r.rebuild_first) {
-    wave_body<ENGINE, GOAL, SD, O, true, true, WPG>(cfg, g0, smem, wg_items);
+  if (r.reset_first) {
+    // The states-only reset of this wave's env, in the wave's own carve: the candidate table and the sampled
+    // positions in the union region (dead until the first capsule test), the obstacle records, agent rows (next-row
+    // slot) and goal rows where the rebuild pass below expects them -- it never reads them back from HBM.  Only
+    // the obstacle records are stored (the episode's output); wave-level syncs only, so the sampler's data-dependent
+    // trip counts meet no workgroup barrier before the rebuild pass's.
+    using C = Carve<SD, O>;
+    static_assert(C::uni_size >= 2 * kSampTab + 4 * NA, "candidate table + sampled positions fit the union region");
+    static_assert(5 * O <= 2 * kSampTab, "the obstacle draws are staged in the candidate table");
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
+    const int64_t env_raw = (int64_t)blockIdx.x * WPG + wid;
+    const bool live = env_raw < g0.n_env;
+    const int64_t env = live ? env_raw : g0.n_env - 1;
+    float* lds = smem + wid * C::total;
+    const float rdv = g0.ray_dirs[lane];
+    const uint64_t seed = r.seed_ptr ? (uint64_t)*r.seed_ptr : r.seed;
+    float* tab = lds + C::uni;
+    float* pos = tab + 2 * kSampTab;
+    sample_states<ENGINE, SD, 64>(cfg, Rng(seed, (uint32_t)(r.env_offset + env)), lane, NA, O, WaveSync{}, tab, pos,
+                                  pos + 2 * NA, lds + C::obst, lds + C::nxt, lds + C::cur + NA * SD, nullptr, nullptr);
+#ifndef DGPPO_DIAG_NOSTORE
+    if (live && lane < O * DGPPO_OBST_FIELDS)
+      const_cast<float*>(g0.obstacles)[env * g0.obstacles_stride + lane] = lds[C::obst + lane];
+#endif
+    reinterpret_cast<float2*>(lds + C::hits)[lane] = make_float2(0.0f, 0.0f);  // no current hits yet (never used)
+    lds[C::rays + lane] = rdv;
+    wave_sync();
   } else {  // stage graph 0's rows exactly as the LOAD prologue of a step does
     using C = Carve<SD, O>;
     constexpr int XS = 16 * SD - 64;
@@ -2028,6 +2070,9 @@ __global__ __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(4))) v
     if (XS > 0) lds[C::cur + xsl] = cv1;
     wave_sync();
   }
+  // graph 0 from the staged rows (sampled above, or a states-only reset's loaded like any graph's): the REBUILD pass
+  // takes them from LDS, as a step takes the previous step's
+  if (r.reset_first | r.rebuild_first) wave_body<ENGINE, GOAL, SD, O, true, false, WPG>(cfg, g0, smem, wg_items);
   // actions arrive in chunks of KC steps staged in LDS, the next chunk loaded into registers one chunk
   // ahead: vmcnt counts stores too, so any wait on an action load also waits for the store drain before
   // it — once per chunk instead of once per step
@@ -2089,6 +2134,7 @@ __global__ __launch_bounds__(64 * WPG) __attribute__((amdgpu_waves_per_eu(4))) v
       wave_sync();
       if (t + KC < r.T) load_chunk(t + KC, cv);
     }
+    ENV_STAMP(15);  // the chunk block alone: every KC-th step its LDS stores wait for the chunk load, i.e. the store drain
     const float* ar = acts + tc * APS + AD * gj;
     const float3 act = make_float3(ar[0], ar[1], AD == 3 ? ar[AD - 1] : 0.0f);
     // this env's rows of step t: base pointers with the env offset folded in and zero env strides (constants
@@ -2590,8 +2636,8 @@ __device__ void make_rectangle(float* rec, float cx, float cy, float w, float h,
 // points do not change and candidate t of the phase is the Philox draw pair at count p + 2 t, so lane l
 // tests candidate b + l of batch b and the phase takes the lowest accepted index (ballot); candidate
 // kMaxIter is taken regardless, as the sequential loop does.  Returns the phase's rejection count.
-constexpr int kSampTab = 256;  // candidate pairs drawn ahead by the whole workgroup (reset LDS tail)
-
+// (kSampTab candidate pairs are drawn ahead by every thread at once: the reset kernel's LDS tail, the rollout wave's
+// union region)
 __device__ int sample_phase(const Rng& rng, uint32_t& count, uint32_t count0, const float* tab, bool goals,
                             float side, int n, float min_dist, float r_in, const float* obst, int O,
                             const float* pts, float& ox, float& oy) {
@@ -2659,22 +2705,26 @@ __device__ void node_goal_rng_wave(Rng& rng, const float* tab, float side, int n
   clear();
   uint32_t count = rng.count;
   const uint32_t count0 = count;
-  // The table's kSampTab candidates as wave bit masks (lane l holds candidates l + 64 q): rejected by an obstacle
+  // The table's kSampTab candidates as per-lane flags (lane l holds candidates l + 64 q): rejected by an obstacle
   // (either phase), out of the area (goal phases), within min_dist of a point placed so far or of the origin (the
   // unplaced rows are zeros).  A candidate's distance test is `min_j d_j <= min_dist`, i.e. `any d_j <= min_dist`
-  // unless some d_j is NaN (min_nan then makes the minimum NaN and the test false): the masks OR in one ballot per
-  // placed point and track NaNs apart, so a phase is a first-set-bit search instead of n distances and O
-  // rectangle tests per candidate -- the same first accepted candidate, the same count.  Past the table (or after
-  // kMaxIter rejections) sample_phase runs as before.
+  // unless some d_j is NaN (min_nan then makes the minimum NaN and the test false): a placed point ORs into each
+  // candidate's `near` flag and NaNs are tracked apart, so a phase is one ballot and a first-set-bit search per 64
+  // candidates instead of n distances and O rectangle tests per candidate -- the same first accepted candidate, the
+  // same count.  Past the table (or after kMaxIter rejections) sample_phase runs as before.
+  // (The flags live in one VGPR, bit 6 q + f: as 24 wave masks they took 48 SGPRs, which the persistent rollout
+  // kernel -- at its VGPR limit, SGPR spills going to VGPR lanes -- does not have.)
   static_assert(kSampTab == 256, "4 candidates per lane");
+  constexpr uint32_t F_INOBS = 0, F_OOB = 1, F_NEAR_A = 2, F_NEAR_G = 3, F_NAN_A = 4, F_NAN_G = 5, F_N = 6;
   float tx[4], ty[4];
-  uint64_t inobs[4], oob[4], nearA[4], nearG[4], nanA[4], nanG[4];
+  uint32_t fl = 0u;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     tx[q] = tab[2 * (lane + 64 * q)];
     ty[q] = tab[2 * (lane + 64 * q) + 1];
-    inobs[q] = __ballot(inside_any(obst, O, tx[q], ty[q], r_in));
-    oob[q] = __ballot(tx[q] < 0.0f || ty[q] < 0.0f || tx[q] > side || ty[q] > side);
+    const bool in = inside_any(obst, O, tx[q], ty[q], r_in);
+    const bool out = tx[q] < 0.0f || ty[q] < 0.0f || tx[q] > side || ty[q] > side;
+    fl |= ((in ? 1u << F_INOBS : 0u) | (out ? 1u << F_OOB : 0u)) << (F_N * q);
   }
   // `norm2(..) <= min_dist` on the squared norms (sq_le_threshold; NaN iff the squared norm is NaN): no root per
   // candidate and placed point
@@ -2683,26 +2733,26 @@ __device__ void node_goal_rng_wave(Rng& rng, const float* tab, float side, int n
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float x = sq2(0.0f - tx[q], 0.0f - ty[q]);
-      nearA[q] = nearG[q] = __ballot(x <= t_le);
-      nanA[q] = nanG[q] = __ballot(x != x);
+      constexpr uint32_t near = 1u << F_NEAR_A | 1u << F_NEAR_G, nan = 1u << F_NAN_A | 1u << F_NAN_G;
+      fl = (fl & ~((near | nan) << (F_N * q))) | (((x <= t_le ? near : 0u) | (x != x ? nan : 0u)) << (F_N * q));
     }
   };
-  auto add_point = [&](uint64_t (&near)[4], uint64_t (&nan)[4], float px, float py) {
+  auto add_point = [&](uint32_t f_near, uint32_t f_nan, float px, float py) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float x = sq2(px - tx[q], py - ty[q]);
-      near[q] |= __ballot(x <= t_le);
-      nan[q] |= __ballot(x != x);
+      fl |= ((x <= t_le ? 1u << f_near : 0u) | (x != x ? 1u << f_nan : 0u)) << (F_N * q);
     }
   };
-  auto phase = [&](bool goals, const float* pts, const uint64_t (&near)[4], const uint64_t (&nan)[4], float& ox,
-                   float& oy) -> int {
+  auto phase = [&](bool goals, const float* pts, uint32_t f_near, uint32_t f_nan, float& ox, float& oy) -> int {
     const int s = (int)((count - count0) / 2u);  // this phase's first candidate
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int lo = s - 64 * q;
       if (lo >= 64) continue;
-      uint64_t good = ~(inobs[q] | (near[q] & ~nan[q]) | (goals ? oob[q] : 0ull));
+      const uint32_t w = fl >> (F_N * q);
+      const bool bad = ((w >> F_INOBS) & 1u) | (((w >> f_near) & 1u) & ~(w >> f_nan) & 1u) | (goals & ((w >> F_OOB) & 1u));
+      uint64_t good = __ballot(!bad);
       if (lo > 0) good &= ~0ull << lo;
       if (good) {
         const int k = 64 * q + __ffsll((unsigned long long)good) - 1;
@@ -2718,19 +2768,19 @@ __device__ void node_goal_rng_wave(Rng& rng, const float* tab, float side, int n
   int agent_id = 0;
   while (agent_id < n) {
     float cx, cy, gx, gy;
-    const int it_agent = phase(false, pos, nearA, nanA, cx, cy);
+    const int it_agent = phase(false, pos, F_NEAR_A, F_NAN_A, cx, cy);
     if (lane == 0) {
       pos[2 * agent_id] = cx;
       pos[2 * agent_id + 1] = cy;
     }
-    add_point(nearA, nanA, cx, cy);
+    add_point(F_NEAR_A, F_NAN_A, cx, cy);
     wv::wave_sync();
-    const int it = phase(true, gl, nearG, nanG, gx, gy);
+    const int it = phase(true, gl, F_NEAR_G, F_NAN_G, gx, gy);
     if (lane == 0) {
       gl[2 * agent_id] = gx;
       gl[2 * agent_id + 1] = gy;
     }
-    add_point(nearG, nanG, gx, gy);
+    add_point(F_NEAR_G, F_NAN_G, gx, gy);
     wv::wave_sync();
     ++agent_id;
     if (it_agent >= kMaxIter || it >= kMaxIter) {  // no solution: start over (utils.py:229-232)
@@ -2776,63 +2826,60 @@ __device__ __forceinline__ void graph_of_staged_rows(const dgppo_env_cfg& cfg, c
   }
 }
 
-template <int ENGINE, int GOAL, int SD, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void env_reset_kernel(dgppo_env_cfg cfg, dgppo_env_reset_io io, int states_only) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+__device__ __forceinline__ void WaveSync::operator()() const { wv::wave_sync(); }
+
+// The states-only half of a reset for one env, by NTHR threads (tid 0..NTHR-1; the first 64 are one wave) that meet
+// at `sync` (BlockSync: the workgroup, NTHR = blockDim.x; WaveSync: NTHR = 64, a lone wave of a larger workgroup):
+// the Lidar obstacle records into `obst`, the sampled positions into pos / gl ((n, 2) each), the agent rows into
+// `nxt` and the goal rows into `goal` ((n, SD) each, headings included), the MPE obstacle rows into `third`.  `tab`:
+// 2 kSampTab floats (the obstacle draws are staged there first).  count_slot: one LDS word, NTHR > 64 only.  Ends
+// behind a sync.
+template <int ENGINE, int SD, int NTHR, class Sync>
+__device__ __forceinline__ void sample_states(const dgppo_env_cfg& cfg, Rng rng, int tid, int n, int O, Sync sync,
+                                              float* tab, float* pos, float* gl, float* obst, float* nxt, float* goal,
+                                              float* third, uint32_t* count_slot) {
   const bool mpe = ENGINE == DGPPO_ENGINE_MPE;
-  const Dims<0, -1, 0, 0> d(cfg);
-  const int n = d.n, O = d.O, k = d.k;
-  const bool lidar = !mpe && O > 0;
-  const Carve cv(n, SD, O, cfg.n_rays, k, !mpe);
-  const int tid = threadIdx.x;
-  const int64_t env = blockIdx.x;
-  float* nxt = lds + cv.nxt;            // sampled agent states
-  float* goal = lds + cv.cur + n * SD;  // sampled goal states
-  float* third = lds + cv.cur + 2 * n * SD;  // MPE obstacle states
-  float* obst = lds + cv.obst;
-  __shared__ uint32_t rng_count;
-  Rng rng(io.seed_ptr ? *io.seed_ptr : io.seed, (uint32_t)(io.env_offset + env));
   const float area = cfg.area_size;
-  float* pos = lds + cv.samp;
-  float* gl = pos + 2 * n;
   // obstacles: draw l of the reference's sequence (centres x / y per obstacle, then sizes, then angles) is the
   // Philox word at count l, so thread l draws it (staged in the candidate table, filled only afterwards) and
   // thread o builds rectangle o -- the same values as one thread drawing them in order
-  float* tab = lds + cv.total;
   const int n_ob_draws = (!mpe && O > 0) ? 5 * O : 0;
-  for (int l = tid; l < n_ob_draws; l += BLOCK) {
+  for (int l = tid; l < n_ob_draws; l += NTHR) {
     Rng r = rng;
     r.count = (uint32_t)l;
     const float lo = l < 2 * O ? 0.0f : (l < 4 * O ? cfg.obs_len_lo : cfg.obs_theta_lo);
     const float hi = l < 2 * O ? area : (l < 4 * O ? cfg.obs_len_hi : cfg.obs_theta_hi);
     tab[l] = r.uniform(lo, hi);
   }
-  __syncthreads();
-  for (int o = tid; o < (n_ob_draws > 0 ? O : 0); o += BLOCK)
+  sync();
+  for (int o = tid; o < (n_ob_draws > 0 ? O : 0); o += NTHR)
     make_rectangle(obst + o * DGPPO_OBST_FIELDS, tab[2 * o], tab[2 * o + 1], tab[2 * O + 2 * o], tab[2 * O + 2 * o + 1],
                    tab[4 * O + o]);
-  if (tid == 0) rng_count = (uint32_t)n_ob_draws;
-  __syncthreads();
+  uint32_t rng_count = (uint32_t)n_ob_draws;
+  sync();
   // the first kSampTab candidate pairs of the sampler's stream, drawn by every thread at once
-  for (int k = tid; k < kSampTab; k += BLOCK) {
+  for (int k = tid; k < kSampTab; k += NTHR) {
     Rng r = rng;
     r.count = rng_count + 2u * (uint32_t)k;
     tab[2 * k] = r.uniform(0.0f, area);
     tab[2 * k + 1] = r.uniform(0.0f, area);
   }
-  __syncthreads();
+  sync();
   if (tid < 64) {  // agent / goal positions: the rejection sampler, one wave wide
     rng.count = rng_count;
     node_goal_rng_wave(rng, tab, area, n, cfg.c_min_dist, cfg.c_inside_r, obst, mpe ? 0 : O, pos, gl);
-    if (tid == 0) rng_count = rng.count;
+    if (NTHR > 64 && tid == 0) *count_slot = rng.count;
   }
-  __syncthreads();
-  for (int idx = tid; idx < n * SD; idx += BLOCK) {
+  sync();
+  // the stream position behind the sampler: wave-uniform in the one wave that ran it, broadcast to any other
+  if constexpr (NTHR > 64) rng_count = *count_slot;
+  else rng_count = (uint32_t)__builtin_amdgcn_readfirstlane((int)rng.count);
+  for (int idx = tid; idx < n * SD; idx += NTHR) {
     const int i = idx / SD, c = idx - (idx / SD) * SD;
     nxt[idx] = c < 2 ? pos[2 * i + c] : 0.0f;
     goal[idx] = c < 2 ? gl[2 * i + c] : 0.0f;
   }
-  __syncthreads();
+  sync();
   if (tid == 0 && (ENGINE == DGPPO_ENGINE_OMNI || mpe)) {
     rng.count = rng_count;
     if (ENGINE == DGPPO_ENGINE_OMNI) {  // chain headings toward the next agent (lidar_omni_target.py:246-272)
@@ -2868,9 +2915,9 @@ __global__ __launch_bounds__(BLOCK) void env_reset_kernel(dgppo_env_cfg cfg, dgp
       }
     }
   }
-  __syncthreads();
+  sync();
   if (ENGINE == DGPPO_ENGINE_BICYCLE) {  // headings: agent i's draw is the Philox word at count rng_count + i
-    for (int i = tid; i < n; i += BLOCK) {
+    for (int i = tid; i < n; i += NTHR) {
       Rng r = rng;
       r.count = rng_count + (uint32_t)i;
       float s, c;
@@ -2878,8 +2925,30 @@ __global__ __launch_bounds__(BLOCK) void env_reset_kernel(dgppo_env_cfg cfg, dgp
       nxt[i * SD + 2] = c;
       nxt[i * SD + 3] = s;
     }
-    __syncthreads();
+    sync();
   }
+}
+
+template <int ENGINE, int GOAL, int SD, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void env_reset_kernel(dgppo_env_cfg cfg, dgppo_env_reset_io io, int states_only) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const bool mpe = ENGINE == DGPPO_ENGINE_MPE;
+  const Dims<0, -1, 0, 0> d(cfg);
+  const int n = d.n, O = d.O, k = d.k;
+  const bool lidar = !mpe && O > 0;
+  const Carve cv(n, SD, O, cfg.n_rays, k, !mpe);
+  const int tid = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  float* nxt = lds + cv.nxt;            // sampled agent states
+  float* goal = lds + cv.cur + n * SD;  // sampled goal states
+  float* third = lds + cv.cur + 2 * n * SD;  // MPE obstacle states
+  float* obst = lds + cv.obst;
+  __shared__ uint32_t rng_count;  // (workgroups of more than one wave: the stream position behind the sampler)
+  Rng rng(io.seed_ptr ? *io.seed_ptr : io.seed, (uint32_t)(io.env_offset + env));
+  float* pos = lds + cv.samp;
+  float* gl = pos + 2 * n;
+  sample_states<ENGINE, SD, BLOCK>(cfg, rng, tid, n, O, BlockSync{}, lds + cv.total, pos, gl, obst, nxt, goal, third,
+                                   &rng_count);
   if (states_only) {  // the wave step kernel builds the graph from these rows (dgppo_env_reset)
     if (lidar) {
       float* ob = io.obstacles + env * io.obstacles_stride;
@@ -3933,13 +4002,15 @@ extern "C" int dgppo_env_rollout_plan(const dgppo_env_cfg* cfg, const dgppo_env_
   if (validate(cfg) || !r || r->T < 0 || r->step.n_env < 0) return DGPPO_EINVAL;
   if (vmas::is_vmas(cfg)) {
     out->route = DGPPO_ENV_ROUTE_VMAS;
+    out->reset_launches = r->reset_first ? 1 : 0;
     return 0;
   }
   const dgppo_env_step_io& io = r->step;
-  if (r->T == 0 && !r->rebuild_first) return 0;
+  if (r->T == 0 && !r->rebuild_first && !r->reset_first) return 0;
   if (io.n_env == 0) return 0;
-  if (!io.states || !io.action || !io.nodes || !io.edges || !io.out_states || !io.receivers || !io.senders ||
-      !io.reward || !io.cost)
+  // (an episode of no steps has no actions, rewards or costs: those buffers may then be empty)
+  if (!io.states || !io.nodes || !io.edges || !io.out_states || !io.receivers || !io.senders ||
+      (r->T > 0 && (!io.action || !io.reward || !io.cost)))
     return DGPPO_EINVAL;
   const bool lidar = cfg->engine != DGPPO_ENGINE_MPE && cfg->n_obs > 0;
   if (lidar && (!io.obstacles || !io.ray_dirs)) return DGPPO_EINVAL;
@@ -3952,12 +4023,15 @@ extern "C" int dgppo_env_rollout_plan(const dgppo_env_cfg* cfg, const dgppo_env_
     pl.threads = 64 * w;
     pl.lds_bytes = (int64_t)w * (int64_t)(cfg->state_dim == 4 ? kRolloutWaveLds<4>
                                           : (cfg->state_dim == 5 ? kRolloutWaveLds<5> : kRolloutWaveLds<kOmniSD>));
-    *out = pl;
+    *out = pl;  // (reset_first: each wave samples its own env inside this launch -- no reset launch)
     return 0;
   }
-  // other configs: rebuild_first: a states-only reset (dgppo_env_reset_states) left graph 0 unbuilt when the
+  // other configs: reset_first launches the reset dgppo_env_reset_states would (states-only where the single-step
+  // wave kernels take the config, else the full reset) and then counts as rebuild_first
+  pl.reset_launches = r->reset_first ? 1 : 0;
+  // rebuild_first: a states-only reset (dgppo_env_reset_states) left graph 0 unbuilt when the
   // wave kernels took it (a misaligned per-step stride sends the rollout here)
-  pl.rebuild = r->rebuild_first && wave_config(cfg, io.edges, io.edges_stride, 0, io.out_states, io.out_states_stride, 0);
+  pl.rebuild = (r->rebuild_first || r->reset_first) && wave_config(cfg, io.edges, io.edges_stride, 0, io.out_states, io.out_states_stride, 0);
   // MPE n = 3 with 3 obstacles (BASELINE config 2): the wave-per-env persistent rollout (graph 0 is loaded: the MPE
   // reset always builds it); DGPPO_MPE_WAVE=0 or the block step kernels forced keep the workgroup-per-env kernel
   if (block_rollout_enabled() && mpe_wave_enabled() && r->T > 0 && mpe_wave_config(cfg) &&
@@ -4013,9 +4087,24 @@ extern "C" int dgppo_env_rollout_plan(const dgppo_env_cfg* cfg, const dgppo_env_
 extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* r, void* stream) {
   dgppo_env_rollout_plan_info pl;
   if (const int rc = dgppo_env_rollout_plan(cfg, r, &pl)) return rc;
+  const dgppo_env_step_io& io = r->step;
+  if (pl.reset_launches) {  // reset_first off the fused route: the reset a dgppo_env_reset_states call launches
+    dgppo_env_reset_io ri{};
+    ri.seed = r->seed;
+    ri.seed_ptr = reinterpret_cast<const uint64_t*>(r->seed_ptr);
+    ri.env_offset = (int32_t)r->env_offset;
+    ri.obstacles = const_cast<float*>(io.obstacles);
+    ri.obstacles_stride = io.obstacles_stride;
+    ri.ray_dirs = io.ray_dirs;
+    ri.nodes = io.nodes, ri.nodes_stride = io.nodes_stride;
+    ri.edges = io.edges, ri.edges_stride = io.edges_stride;
+    ri.out_states = io.out_states, ri.out_states_stride = io.out_states_stride;
+    ri.receivers = io.receivers, ri.senders = io.senders, ri.edge_index_stride = io.edge_index_stride;
+    ri.n_env = io.n_env;
+    if (const int rc = dgppo_env_reset_states(cfg, &ri, stream)) return rc;
+  }
   if (pl.route == DGPPO_ENV_ROUTE_VMAS) return vmas::rollout(cfg, r, stream);
   if (pl.route == DGPPO_ENV_ROUTE_NONE) return 0;
-  const dgppo_env_step_io& io = r->step;
   const hipStream_t s = (hipStream_t)stream;
   if (pl.route == DGPPO_ENV_ROUTE_LIDAR_WAVE) {
     visit_engine_goal(*cfg, [&](auto e) {
@@ -4024,7 +4113,11 @@ extern "C" int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollo
     });
     return (int)hipGetLastError();
   }
-  if (pl.rebuild) launch_rebuild(cfg, io, s);
+  if (pl.rebuild) {
+    dgppo_env_step_io st = io;
+    if (!st.action) st.action = st.states, st.action_stride = st.states_stride;  // T == 0: read, never used
+    launch_rebuild(cfg, st, s);
+  }
   if (pl.route == DGPPO_ENV_ROUTE_MPE_WAVE) {
     const dim3 grid((unsigned)pl.grid), block((unsigned)pl.threads);
     const size_t sh = (size_t)pl.lds_bytes;

@@ -324,18 +324,25 @@ class MultiAgentEnv(ABC):
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, ob)
 
     def rollout_into(self, buf: GraphsTuple, obstacles: Optional[torch.Tensor], actions: torch.Tensor,
-                     rewards: torch.Tensor, costs: torch.Tensor, rebuild_first: bool = False) -> None:
+                     rewards: torch.Tensor, costs: torch.Tensor, rebuild_first: bool = False, reset_key=None,
+                     env_offset: int = 0) -> None:
         """T env steps with the given actions (T, B, n, A) in one call (torch.ops.dgppo.env_rollout): buf is
         a time-major (T+1, B, ...) graph buffer, step t reads buf[t] and writes buf[t+1], rewards[t],
-        costs[t] -- the env half of the reference's rollout scan (trainer/utils.py:45-55)."""
+        costs[t] -- the env half of the reference's rollout scan (trainer/utils.py:45-55).
+        reset_key (an int, or a 1-element int64 device tensor read at run time): the call first resets the envs as
+        `reset_states(reset_key, env_offset=env_offset)` + rebuild_first would -- `obstacles` receives the records
+        -- inside the same launch where the persistent Lidar kernel runs."""
         _lib.require_gpu(buf.states.device, "env.rollout")
         n, A = self._num_agents, self.action_dim
         T = actions.shape[0]
         if actions.shape[-2:] != (n, A) or buf.states.shape[0] != T + 1 or buf.states.dim() != 4:
             raise ValueError("rollout_into: actions (T, B, n, A) and a (T+1, B, N, sd) graph buffer")
+        tkey = reset_key if isinstance(reset_key, torch.Tensor) else None
+        seed = 0 if tkey is not None or reset_key is None else int(reset_key) & 0xFFFFFFFFFFFFFFFF
         torch.ops.dgppo.env_rollout(self._cfg_handle, bool(rebuild_first), obstacles, actions,
                                     self._ray_table(buf.states.device), buf.nodes, buf.edges, buf.states,
-                                    buf.receivers, buf.senders, rewards, costs)
+                                    buf.receivers, buf.senders, rewards, costs, reset_key is not None, tkey,
+                                    seed if seed < 2 ** 63 else seed - 2 ** 64, int(env_offset))
 
     def step_into(self, graph: GraphsTuple, action: torch.Tensor, out: GraphsTuple,
                   reward: torch.Tensor, cost: torch.Tensor) -> GraphsTuple:

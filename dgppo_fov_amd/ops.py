@@ -168,21 +168,26 @@ def _env_reset_states_fake(cfg, key, seed, env_offset, n_env, obstacles, ray_dir
     return None
 
 
-@torch.library.custom_op("dgppo::env_rollout", mutates_args=("nodes", "edges", "states", "receivers", "senders",
-                                                              "reward", "cost"))
+@torch.library.custom_op("dgppo::env_rollout", mutates_args=("obstacles", "nodes", "edges", "states", "receivers",
+                                                              "senders", "reward", "cost"))
 def env_rollout(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor], actions: Tensor, ray_dirs: Tensor,
                 nodes: Tensor, edges: Tensor, states: Tensor, receivers: Tensor, senders: Tensor, reward: Tensor,
-                cost: Tensor) -> None:
+                cost: Tensor, reset_first: bool = False, key: Optional[Tensor] = None, seed: int = 0,
+                env_offset: int = 0) -> None:
     """T env steps with given actions (T, B, n, A) through time-major graph buffers (T+1, B, ...):
     step t reads graph t and writes graph t+1, reward[t] (T, B), cost[t] (T, B, n, n_cost).
-    rebuild_first: graph 0's rows are first built from its agent / goal states (env_reset_states)."""
+    rebuild_first: graph 0's rows are first built from its agent / goal states (env_reset_states).
+    reset_first: env_reset_states (key / seed / env_offset as there; `obstacles` is written) + rebuild_first in the
+    same call -- inside the one launch on the persistent Lidar route."""
     _lib.require_gpu(states.device, "dgppo::env_rollout")
-    r = _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost)
+    r = _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost,
+                    reset_first, key, seed, env_offset)
     _lib.check(_lib.load().dgppo_env_rollout(ctypes.byref(env_cfg(cfg)), ctypes.byref(r), _stream(states)),
                "dgppo_env_rollout")
 
 
-def _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost):
+def _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost,
+                reset_first=False, key=None, seed=0, env_offset=0):
     """The dgppo_env_rollout_io of env_rollout's tensors (env_rollout and env_rollout_plan both build it here)."""
     T = int(actions.shape[0])
     if states.shape[0] != T + 1 or reward.shape[0] != T or cost.shape[0] != T:
@@ -192,7 +197,8 @@ def _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, state
     io.states, io.states_stride = _p(states), _stride(states[0], 2)
     io.obstacles = _p(obstacles)
     io.obstacles_stride = obstacles.stride(-3) if obstacles is not None else 0
-    io.action, io.action_stride = _p(actions), _stride(actions[0], 2)
+    # per env within a step; an episode of no steps (T = 0) has no action / cost element, so no strides to hold
+    io.action, io.action_stride = _p(actions), (_stride(actions, 2) if T else 0)
     io.ray_dirs = _p(ray_dirs)
     io.nodes, io.nodes_stride = _p(nodes), _stride(nodes[0], 2)
     io.edges, io.edges_stride = _p(edges), _stride(edges[0], 2)
@@ -200,23 +206,31 @@ def _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, state
     io.receivers, io.senders = _p(receivers), _p(senders)
     io.edge_index_stride = _stride(receivers[0], 1)
     io.reward, io.reward_stride = _p(reward), reward.stride(1)
-    io.cost, io.cost_stride = _p(cost), _stride(cost[0], 2)
+    io.cost, io.cost_stride = _p(cost), (_stride(cost, 2) if T else 0)
     io.n_env = int(states.shape[1])
     r.T, r.rebuild_first = T, int(bool(rebuild_first))
     r.t_states, r.t_nodes, r.t_edges = states.stride(0), nodes.stride(0), edges.stride(0)
     if receivers.stride(0) != senders.stride(0):
         raise ValueError("env_rollout: receivers and senders need the same time stride")
     r.t_index, r.t_action, r.t_reward, r.t_cost = receivers.stride(0), actions.stride(0), reward.stride(0), cost.stride(0)
+    r.reset_first, r.env_offset = int(bool(reset_first)), int(env_offset)
+    if key is not None:
+        if key.device != states.device or key.numel() != 1 or key.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("tensor key must be a 1-element int64 tensor on the env's device")
+        r.seed, r.seed_ptr = 0, key.data_ptr()
+    else:
+        r.seed, r.seed_ptr = int(seed) & 0xFFFFFFFFFFFFFFFF, None
     return r
 
 
 def env_rollout_plan(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor], actions: Tensor, ray_dirs: Tensor,
                      nodes: Tensor, edges: Tensor, states: Tensor, receivers: Tensor, senders: Tensor, reward: Tensor,
-                     cost: Tensor) -> _lib.EnvRolloutPlan:
+                     cost: Tensor, reset_first: bool = False) -> _lib.EnvRolloutPlan:
     """The route env_rollout would take for these tensors (dgppo_env_rollout_plan: the kernel family, envs per
     workgroup, block sizes, action staging, grid and LDS), without launching anything.  Tensors on any device: only
     their addresses' alignment and strides are read."""
-    r = _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost)
+    r = _rollout_io(rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders, reward, cost,
+                    reset_first)
     pl = _lib.EnvRolloutPlan()
     _lib.check(_lib.load().dgppo_env_rollout_plan(ctypes.byref(env_cfg(cfg)), ctypes.byref(r), ctypes.byref(pl)),
                "dgppo_env_rollout_plan")
@@ -225,7 +239,7 @@ def env_rollout_plan(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor],
 
 @env_rollout.register_fake
 def _env_rollout_fake(cfg, rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders,
-                      reward, cost) -> None:
+                      reward, cost, reset_first=False, key=None, seed=0, env_offset=0) -> None:
     return None
 
 

@@ -39,8 +39,9 @@ class RolloutEngine:
         overlap the other's compute (envs are independent: results are identical).  With an actor
         this needs the fused policy step (it reads only the prepared query-key workspace); the T
         sampling-noise tensors are drawn up front with the same Philox stream ids.
-        fused: an env-only (MODE_RANDOM, one lane) rollout runs as a states-only reset plus one persistent
-        dgppo_env_rollout launch for all T steps (else reset + T step launches; identical results).
+        fused: an env-only (MODE_RANDOM, one lane) rollout runs as one dgppo_env_rollout call with reset_first -- on
+        the persistent Lidar route one launch that samples the envs and runs all T steps (else reset + T step
+        launches; identical results).
         init_state: the env's state tuple (agent, goal, obstacle) for the n_env envs (env.get_graph's argument);
         when given, every run starts from that scene instead of a reset (the key then only seeds the policy
         noise).  The fp32 device tensors are read in place on every run, so editing them between runs -- also
@@ -150,11 +151,11 @@ class RolloutEngine:
                     cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
             return
         if self.mode == self.MODE_RANDOM and self.lanes == 1 and self.fused:
-            # env-only rollout: the states-only reset + ONE persistent launch for all T steps (graph 0 built
-            # by the rollout kernel; configs without it loop the step kernel inside the call)
-            env.reset_states(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
-                             obstacles_out=self.obstacles)
-            env.rollout_into(self.buf, self.obstacles, self.actions, self.rewards, self.costs, rebuild_first=True)
+            # env-only rollout: ONE call, on the persistent Lidar route one launch -- each wave samples its env (the
+            # states-only reset), builds graph 0 and runs all T steps; other configs launch the reset, then their
+            # rollout kernel or step loop, inside the call
+            env.rollout_into(self.buf, self.obstacles, self.actions, self.rewards, self.costs, reset_key=self.key,
+                             env_offset=self.env_offset)
             return
         cur = env.reset(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
                         obstacles_out=self.obstacles)

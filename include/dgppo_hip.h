@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define DGPPO_ABI_VERSION 14  /* 14: dgppo_gnn_layer_bwd removed (the fused layer backward measured slower than the attention backward + GEMMs), dgppo_gnn_set_attn_kernel removed with the graph-form MFMA attention kernels (2-5x slower); 13: dgppo_gemm_wgrad_grouped (a pass's weight gradients in one launch); 12: dgppo_adam_multi (the clipped Adam steps of several nets in two launches); 11: dgppo_gnn_layer_fwd (fused GraphTransformer layer forward); 10: in-kernel policy-step noise, dgppo_gnn_set_graph_otf; 9: dgppo_gnn_set_attn_kernel (graph-form MFMA attention selector); 8: VMAS engines (DGPPO_ENGINE_VMAS_*) through the dgppo_env_* entry points; 7: dgppo_lstm_cell_fwd / _bwd; 6: env variants (dgppo_env_cfg variant fields); 5: Q-free attention args (beta, qt/dqt/dbeta strides), dgppo_gather_env_steps; 4: dgppo_env_rollout, dgppo_env_reset_states; 3: dgppo_adam takes double b1 / b2; 2: dgppo_gnn_attn_args.da_add, wide-edge entry points, env cfg Omni fields */
+#define DGPPO_ABI_VERSION 14  /* 14 (still): dgppo_env_rollout_io gained reset_first / seed / seed_ptr / env_offset at its end (the states-only reset inside the rollout launch) and dgppo_env_rollout_plan_info reset_launches -- a caller built against the shorter structs must be rebuilt; 14: dgppo_gnn_layer_bwd removed (the fused layer backward measured slower than the attention backward + GEMMs), dgppo_gnn_set_attn_kernel removed with the graph-form MFMA attention kernels (2-5x slower); 13: dgppo_gemm_wgrad_grouped (a pass's weight gradients in one launch); 12: dgppo_adam_multi (the clipped Adam steps of several nets in two launches); 11: dgppo_gnn_layer_fwd (fused GraphTransformer layer forward); 10: in-kernel policy-step noise, dgppo_gnn_set_graph_otf; 9: dgppo_gnn_set_attn_kernel (graph-form MFMA attention selector); 8: VMAS engines (DGPPO_ENGINE_VMAS_*) through the dgppo_env_* entry points; 7: dgppo_lstm_cell_fwd / _bwd; 6: env variants (dgppo_env_cfg variant fields); 5: Q-free attention args (beta, qt/dqt/dbeta strides), dgppo_gather_env_steps; 4: dgppo_env_rollout, dgppo_env_reset_states; 3: dgppo_adam takes double b1 / b2; 2: dgppo_gnn_attn_args.da_add, wide-edge entry points, env cfg Omni fields */
 #define DGPPO_EINVAL (-22)
 
 /* engines */
@@ -248,6 +248,11 @@ int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_args* a, vo
  * buffer), the actions of step t at action + t * t_action, reward[t] / cost[t] at + t * t_reward /
  * t_cost.  Step t reads graph t and writes graph t+1, reward[t], cost[t]; rebuild_first = 1 first
  * writes graph 0's rows from its agent / goal states and obstacles (after dgppo_env_reset_states).
+ * reset_first = 1: the call is dgppo_env_reset_states (key `seed`, or *seed_ptr when non-NULL -- a device scalar read
+ * at kernel start, so a captured hipGraph replays with the key it is given --, env b drawing from env_offset + b)
+ * followed by rebuild_first = 1, bit for bit in every output; step.obstacles is then WRITTEN (the obstacle records)
+ * before it is read.  The LIDAR_WAVE route samples inside its one launch (each wave draws its own env and keeps the
+ * rows in LDS); every other route launches the reset dgppo_env_reset_states would.  All-zero new fields: as before.
  * Lidar configs at n = 8, 32 rays, top-8, 3 obstacles run one persistent kernel (a wave per env for
  * all T steps, state in LDS); most others a persistent workgroup-per-env kernel, the rest loop dgppo_env_step
  * (identical results; dgppo_env_rollout_plan below names the route). */
@@ -256,6 +261,11 @@ typedef struct dgppo_env_rollout_io {
   int32_t T;
   int32_t rebuild_first;
   int64_t t_states, t_nodes, t_edges, t_index, t_action, t_reward, t_cost;
+  int32_t reset_first;      /* sample the envs first (dgppo_env_reset_states + rebuild_first) */
+  int32_t pad_;
+  uint64_t seed;
+  const int64_t* seed_ptr;  /* optional device scalar; when non-NULL it overrides `seed` */
+  int64_t env_offset;
 } dgppo_env_rollout_io;
 
 int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* io, void* stream);
@@ -263,7 +273,7 @@ int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* io, 
 /* The host decisions of a dgppo_env_rollout(cfg, io) call, without launching anything (no HIP call: needs no GPU);
  * dgppo_env_rollout launches from this struct.  Pointers are read for NULL and alignment only.  Returns DGPPO_EINVAL
  * exactly where dgppo_env_rollout would (route is then NONE), else 0.  The routes, in the order they are tried:
- *   NONE        T == 0 without rebuild_first, or n_env == 0: nothing is launched
+ *   NONE        T == 0 without rebuild_first / reset_first, or n_env == 0: nothing is launched
  *   VMAS        the VMAS engines' own rollout (csrc/vmas.hip); nothing else is filled
  *   LIDAR_WAVE  wave-per-env persistent kernel: Lidar engines, no variant, n = 8, 32 rays, top-8, 3 obstacles, step
  *               kernel mode auto, edge rows (base, per-env and per-step stride) 16-byte aligned (8-byte for
@@ -278,8 +288,9 @@ int dgppo_env_rollout(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* io, 
  *               dgppo_env_step call decides again from its own pointers, so with a per-step stride that breaks the
  *               wave kernels' alignment later steps can run another step kernel than the first (same results)
  * rebuild = 1: a launch of the wave step kernel in REBUILD mode builds graph 0 first (rebuild_first set, the config
- * is the single-step wave kernel's, LIDAR_WAVE was not taken).  The two environment knobs are read once per
- * process. */
+ * is the single-step wave kernel's, LIDAR_WAVE was not taken).  reset_launches = 1: reset_first is set and a reset
+ * launch (dgppo_env_reset_states) precedes everything else; 0 on LIDAR_WAVE, whose kernel samples itself.  The two
+ * environment knobs are read once per process. */
 #define DGPPO_ENV_ROUTE_NONE 0
 #define DGPPO_ENV_ROUTE_VMAS 1
 #define DGPPO_ENV_ROUTE_LIDAR_WAVE 2
@@ -297,6 +308,8 @@ typedef struct dgppo_env_rollout_plan_info {
   int32_t pad_;
   int64_t grid;           /* workgroups of the main launch */
   int64_t lds_bytes;      /* its dynamic LDS */
+  int32_t reset_launches; /* reset_first: reset launches before the main launch (0: sampled inside it) */
+  int32_t pad2_;
 } dgppo_env_rollout_plan_info;
 int dgppo_env_rollout_plan(const dgppo_env_cfg* cfg, const dgppo_env_rollout_io* io, dgppo_env_rollout_plan_info* out);
 

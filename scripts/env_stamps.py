@@ -18,7 +18,8 @@ from dgppo_fov_amd.trainer.rollout import RolloutEngine  # noqa: E402
 PHASES = ["A: action, LDS staging", "B: dynamics, distances", "C: cost, reward", "F1 packet 1 (agent-agent edges)",
           "D: is-inside, culling masks", "packet 2 (agent-goal edges)", "capsule tests, item list",
           "packet 3 (agent/goal node+state rows)", "barrier 1 wait", "pooled ray cast", "packet 4 (hit-row constants)",
-          "barrier 2 wait", "E: sort keys, miss ranks", "E: ranks of the hits", "F2: lidar columns"]
+          "barrier 2 wait", "E: sort keys, miss ranks", "E: ranks of the hits", "F2: lidar columns",
+          "action chunk (every 16th step: its LDS staging waits for the chunk load behind the store drain)"]
 
 
 def main():

@@ -9,19 +9,28 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = open(os.path.join(ROOT, "dgppo_fov_amd/csrc/env_step.hip")).read()
-k0 = src.index("void env_reset_kernel(dgppo_env_cfg cfg, dgppo_env_reset_io io, int states_only) {")
-b0 = src.index("{", k0) + 1
-src = src[:b0] + """
+RSTAMP = """
   uint64_t rs_t = __builtin_amdgcn_s_memtime();
+#ifndef RSTAMP
 #define RSTAMP(k) do { if (threadIdx.x == 0) { const uint64_t now_ = __builtin_amdgcn_s_memtime(); \\
     atomicAdd(&wv::g_env_stamps[k], (unsigned long long)(now_ - rs_t)); rs_t = now_; } } while (0)
-""" + src[b0:]
-marks = [("  if (tid == 0) rng_count = (uint32_t)n_ob_draws;\n  __syncthreads();\n", 0),
-         ("    tab[2 * k + 1] = r.uniform(0.0f, area);\n  }\n  __syncthreads();\n", 1),
-         ("    if (tid == 0) rng_count = rng.count;\n  }\n  __syncthreads();\n", 2),
-         ("    goal[idx] = c < 2 ? gl[2 * i + c] : 0.0f;\n  }\n  __syncthreads();\n", 3),
+#endif
+"""
+# the sampling phases live in sample_states (shared with the persistent rollout's reset_first prologue), the store /
+# graph phases in env_reset_kernel: each gets its own running stamp
+k0 = src.index("__device__ __forceinline__ void sample_states(const dgppo_env_cfg& cfg, Rng rng, int tid, int n, int O, "
+               "Sync sync,\n", src.index("__device__ __forceinline__ void WaveSync::operator()"))
+b0 = src.index("{", k0) + 1
+src = src[:b0] + RSTAMP + src[b0:]
+k1 = src.index("void env_reset_kernel(dgppo_env_cfg cfg, dgppo_env_reset_io io, int states_only) {")
+b1 = src.index("{", k1) + 1
+src = src[:b1] + RSTAMP + src[b1:]
+marks = [("  uint32_t rng_count = (uint32_t)n_ob_draws;\n  sync();\n", 0),
+         ("    tab[2 * k + 1] = r.uniform(0.0f, area);\n  }\n  sync();\n", 1),
+         ("    if (NTHR > 64 && tid == 0) *count_slot = rng.count;\n  }\n  sync();\n", 2),
+         ("    goal[idx] = c < 2 ? gl[2 * i + c] : 0.0f;\n  }\n  sync();\n", 3),
          ("        for (int c = 0; c < SD; ++c) third[o * SD + c] = c == 0 ? cx : (c == 1 ? cy : 0.0f);\n"
-          "      }\n    }\n  }\n  __syncthreads();\n", 4),
+          "      }\n    }\n  }\n  sync();\n", 4),
          ("  if (states_only) {  // the wave step kernel builds the graph from these rows (dgppo_env_reset)\n", 5),
          ("  graph_of_staged_rows<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);\n", 7)]  # (ray cast + graph)
 pos = b0
