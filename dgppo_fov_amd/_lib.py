@@ -154,6 +154,17 @@ class RenderArgs(ctypes.Structure):  # dgppo_render_args
     ]
 
 
+RENDER_MAX_BANDS = 32  # include/dgppo_hip.h DGPPO_RENDER_MAX_BANDS
+
+
+class RenderField(ctypes.Structure):  # dgppo_render_field
+    _fields_ = [
+        ("values", c_f32p), ("gx", ctypes.c_int32), ("gy", ctypes.c_int32),
+        ("extent", ctypes.c_float * 4), ("half_range", ctypes.c_float), ("bands", ctypes.c_int32),
+        ("palette", c_f32p), ("alpha", ctypes.c_float), ("line_halfwidth", ctypes.c_float),
+    ]
+
+
 class EnvRolloutIO(ctypes.Structure):
     _fields_ = [
         ("step", EnvStepIO),
@@ -361,6 +372,8 @@ SIGNATURES = {
     "dgppo_env_get_graph": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphIO), ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
+    "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),
+                                                 ctypes.POINTER(RenderField), ctypes.c_void_p]),
     "dgppo_gemm_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs)]),
     "dgppo_gemm_wgrad_grouped_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs), ctypes.c_int]),
     "dgppo_gemm_wgrad_grouped": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_int, c_f32p, ctypes.c_void_p]),

@@ -260,6 +260,16 @@ class DGPPO:
         a, _, h2 = self.actor.act(g, h, 0)
         return a.view(B, n, -1), self._unrows(h2.view(B, n, -1))
 
+    def get_Vh(self, graph, rnn_state: torch.Tensor, params=None) -> torch.Tensor:
+        """The constraint values of a batch of graphs (dgppo.py:128-134): graph with batch shape (B,), rnn_state
+        (B, rnn_layers, n, carries, 64) as `act` takes it -> Vh (B, n, n_cost), one forward pass of the Vh network."""
+        self._check_params(params)
+        g = self._gb(graph)
+        B, n = g.G, self._n_agents
+        h = self._rows(rnn_state).reshape(B * n, -1).contiguous()
+        v, _ = self.Vh.fwd(g, h, keep_cache=False)
+        return v.view(B, n, -1)
+
     def step(self, graph, rnn_state: torch.Tensor, key: int, params=None):
         """sample_action: (action, log_pi (B, n), rnn)."""
         g = self._gb(graph)

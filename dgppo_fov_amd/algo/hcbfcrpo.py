@@ -21,6 +21,10 @@ class HCBFCRPO(InforMARL):
         c.pop("lr_Vh", None)
         return c
 
+    def get_Vh(self, graph, rnn_state=None, params=None) -> torch.Tensor:
+        """The hand-crafted CBF: the env's own cost of each graph (hcbfcrpo.py:90-93), (B, n, n_cost)."""
+        return self._env.get_cost(graph)
+
     def _final_cost(self, rollout: Rollout) -> torch.Tensor:
         """env.get_cost of next_graph[:, -1] (B, n, n_cost)."""
         ng = rollout.next_graph

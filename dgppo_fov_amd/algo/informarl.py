@@ -32,6 +32,12 @@ class InforMARL(DGPPO):
             c.pop(k, None)
         return c
 
+    @property
+    def get_Vh(self):
+        """InforMARL has no constraint-value function (the reference's informarl.py defines no get_Vh): the name
+        DGPPO provides is absent here, so `hasattr(algo, "get_Vh")` is False.  HCBF-CRPO defines its own."""
+        raise AttributeError(f"{type(self).__name__} has no get_Vh")
+
     def cost_weight_at(self, step: int) -> float:
         """optax.piecewise_constant_schedule(cost_weight, {0.5 T: 5, 0.75 T: 5}) (informarl.py:189-198)."""
         w = self.cost_weight

@@ -17,6 +17,13 @@
 // below by the distance to its bounding circle / box, and the four signed distances are exact, hence 1-Lipschitz),
 // i.e. coverage exactly 0, so culling never changes a byte.  No atomics, no data-dependent ordering: two launches give
 // identical bytes.
+//
+// Layer 0, optional (dgppo_render_frames_field): a scalar field on a uniform Gx x Gy grid, drawn UNDER every other
+// layer -- the reference's contourf + zero-level contour (plot.py viz_opts["cbf"]) by this project's own rule.  A
+// pixel centre inside the grid's extent interpolates its cell's four nodes bilinearly, takes one of K hard-edged
+// bands of a red-to-blue palette (staged in LDS) at alpha 0.9 on white, and is then covered by the black zero line
+// where |val| / |grad val|, the first-order distance to the zero level, is within the line's half-width.  A pixel
+// outside the extent, or in a cell with a non-finite node, stays white.  The pixel loop then starts from that colour.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -51,6 +58,11 @@ struct Params {
   int32_t n, ng, O, N, E, sd;
   int32_t nA, nB, nC, nD, nE;  // primitives per layer: MPE circles, wedges, edges, goal + agent circles, rectangles
   float L, h, inv_h, car_r, obs_r, fov_r, sin_b, cos_b, edge_hw;
+  // layer 0 (render_kernel<true> only): frame f reads the (gy, gx) nodes at field + f * gy * gx
+  const float* field;
+  const float* palette;  // (bands, 3)
+  int32_t gx, gy, bands;
+  float fx0, fy0, inv_dx, inv_dy, f_half, inv_band, f_alpha, line_hw, grad_eps;
 };
 
 __device__ __forceinline__ bool fin(float x) { return fabsf(x) <= 3.4028234664e38f; }  // false for NaN / inf
@@ -144,9 +156,40 @@ __device__ __forceinline__ float distance(const Prim& q, int shape, float px, fl
   return fmaxf(l, m * sgn(P.cos_b * v - P.sin_b * u));
 }
 
+// Layer 0 at pixel centre (px, py): the colour the pixel starts from.  `pal` is the palette in LDS.
+__device__ __forceinline__ void field_colour(const Params& P, const float* __restrict__ fv, const float* pal, float px,
+                                             float py, float& r, float& g, float& b) {
+  const float u = (px - P.fx0) * P.inv_dx, v = (py - P.fy0) * P.inv_dy;
+  const float umax = (float)(P.gx - 1), vmax = (float)(P.gy - 1);
+  if (!(u >= 0.0f && u <= umax && v >= 0.0f && v <= vmax)) return;  // outside (u, v are finite: the extent is)
+  const float fi = fminf(floorf(u), umax - 1.0f), fj = fminf(floorf(v), vmax - 1.0f);  // in [0, g - 2]
+  const int i = (int)fi, j = (int)fj;
+  const float* c = fv + (int64_t)j * P.gx + i;
+  const float v00 = c[0], v10 = c[1], v01 = c[P.gx], v11 = c[P.gx + 1];
+  if (!(fin(v00) && fin(v10) && fin(v01) && fin(v11))) return;
+  const float tx = u - fi, ty = v - fj;
+  const float lo = v00 + tx * (v10 - v00), hi = v01 + tx * (v11 - v01);
+  const float val = lo + ty * (hi - lo);
+  const float gx = ((v10 - v00) + ty * ((v11 - v01) - (v10 - v00))) * P.inv_dx, gy = (hi - lo) * P.inv_dy;
+  const float s = (val + P.f_half) * P.inv_band;
+  const int band = (int)fminf(fmaxf(floorf(s), 0.0f), (float)(P.bands - 1));  // NaN -> 0: never out of the palette
+  r += P.f_alpha * (pal[3 * band] - r);
+  g += P.f_alpha * (pal[3 * band + 1] - g);
+  b += P.f_alpha * (pal[3 * band + 2] - b);
+  const float gn = sqrtf(gx * gx + gy * gy);
+  if (gn * P.L > P.grad_eps) {  // the zero line, black, alpha 1
+    const float w = fminf(fmaxf(0.5f - (fabsf(val) / gn - P.line_hw) * P.inv_h, 0.0f), 1.0f);
+    r -= w * r;
+    g -= w * g;
+    b -= w * b;
+  }
+}
+
+template <bool kField>
 __global__ __launch_bounds__(kThreads) void render_kernel(const Params P) {
   __shared__ Prim list[kThreads];
   __shared__ int wave_count[kThreads / 64];
+  __shared__ float pal[3 * DGPPO_RENDER_MAX_BANDS];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int frame = blockIdx.x / P.tiles_per_frame, tile = blockIdx.x % P.tiles_per_frame;
@@ -165,6 +208,13 @@ __global__ __launch_bounds__(kThreads) void render_kernel(const Params P) {
   for (int j = 0; j < kPix; ++j) {
     py[j] = ((float)(P.S - (row0 + kRowStep * j)) - 0.5f) * P.h;
     cr[j] = cg[j] = cb[j] = 1.0f;
+  }
+  if constexpr (kField) {
+    if (tid < 3 * P.bands) pal[tid] = P.palette[tid];
+    __syncthreads();
+    const float* fv = P.field + (int64_t)frame * P.gy * P.gx;
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) field_colour(P, fv, pal, px, py[j], cr[j], cg[j], cb[j]);
   }
   // the tile's pixel centres span [x0, x1] x [y0, y1]
   const int c1 = min(tx * kTileW + kTileW, P.S), r1 = min(ty * kTileH + kTileH, P.S);
@@ -240,8 +290,24 @@ void span(const void* p, int64_t elems, int64_t episodes, int64_t es, int64_t fp
 }  // namespace dgppo
 
 extern "C" int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_args* a, void* stream) {
+  return dgppo_render_frames_field(cfg, a, nullptr, stream);
+}
+
+extern "C" int dgppo_render_frames_field(const dgppo_env_cfg* cfg, const dgppo_render_args* a,
+                                         const dgppo_render_field* fld, void* stream) {
   using namespace dgppo;
   if (!cfg || !a) return DGPPO_EINVAL;
+  if (fld) {
+    if (!fld->values || !fld->palette || fld->gx < 2 || fld->gy < 2 || fld->gx > 32768 || fld->gy > 32768)
+      return DGPPO_EINVAL;
+    if (fld->bands < 2 || fld->bands > DGPPO_RENDER_MAX_BANDS) return DGPPO_EINVAL;
+    for (int i = 0; i < 4; ++i)
+      if (!isfinite(fld->extent[i])) return DGPPO_EINVAL;
+    if (!(fld->extent[1] > fld->extent[0]) || !(fld->extent[3] > fld->extent[2])) return DGPPO_EINVAL;
+    if (!isfinite(fld->half_range) || !(fld->half_range > 0.0f)) return DGPPO_EINVAL;
+    if (!(fld->alpha >= 0.0f && fld->alpha <= 1.0f) || !isfinite(fld->line_halfwidth) || fld->line_halfwidth < 0.0f)
+      return DGPPO_EINVAL;
+  }
   if (vmas::is_vmas(cfg)) return DGPPO_EINVAL;  // the VMAS reference renderers are separate code
   if (cfg->engine < DGPPO_ENGINE_LIDAR || cfg->engine > DGPPO_ENGINE_OMNI) return DGPPO_EINVAL;
   const bool mpe = cfg->engine == DGPPO_ENGINE_MPE, omni = cfg->engine == DGPPO_ENGINE_OMNI;
@@ -264,14 +330,18 @@ extern "C" int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_
   if (F * tiles_x * tiles_y > 0x7fffffffLL) return DGPPO_EINVAL;
   {  // `out` must not overlap the bytes an input spans
     const uintptr_t o0 = (uintptr_t)a->out, o1 = o0 + (uintptr_t)(F * S * S * 4);
-    uintptr_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+    uintptr_t lo[6] = {0, 0, 0, 0, 0, 0}, hi[6] = {0, 0, 0, 0, 0, 0};
     span(a->states, (int64_t)N * sd, episodes, a->states_estride, fl, a->states_tstride, &lo[0], &hi[0]);
     if (E > 0) {
       span(a->receivers, E, episodes, a->index_estride, fl, a->index_tstride, &lo[1], &hi[1]);
       span(a->senders, E, episodes, a->index_estride, fl, a->index_tstride, &lo[2], &hi[2]);
     }
     if (rects) span(a->obstacles, (int64_t)O * DGPPO_OBST_FIELDS, episodes, a->obstacles_estride, 1, 0, &lo[3], &hi[3]);
-    for (int i = 0; i < 4; ++i)
+    if (fld) {
+      span(fld->values, (int64_t)fld->gx * fld->gy, F, (int64_t)fld->gx * fld->gy, 1, 0, &lo[4], &hi[4]);
+      span(fld->palette, 3 * (int64_t)fld->bands, 1, 0, 1, 0, &lo[5], &hi[5]);
+    }
+    for (int i = 0; i < 6; ++i)
       if (lo[i] < o1 && o0 < hi[i]) return DGPPO_EINVAL;
   }
   Params P{};
@@ -293,6 +363,20 @@ extern "C" int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_
   const double beta = (double)cfg->fov_angle_deg * (3.14159265358979323846 / 180.0);
   P.sin_b = (float)sin(beta), P.cos_b = (float)cos(beta);
   P.edge_hw = cfg->area_size / 720.0f;  // the reference's 2 pt line on its 10 in figure
-  hipLaunchKernelGGL(render_kernel, dim3((unsigned)(F * tiles_x * tiles_y)), dim3(kThreads), 0, (hipStream_t)stream, P);
+  const dim3 grid((unsigned)(F * tiles_x * tiles_y));
+  if (!fld) {
+    hipLaunchKernelGGL(render_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, P);
+    return (int)hipGetLastError();
+  }
+  P.field = fld->values, P.palette = fld->palette;
+  P.gx = fld->gx, P.gy = fld->gy, P.bands = fld->bands;
+  P.fx0 = fld->extent[0], P.fy0 = fld->extent[2];
+  P.inv_dx = (float)((double)(fld->gx - 1) / ((double)fld->extent[1] - (double)fld->extent[0]));
+  P.inv_dy = (float)((double)(fld->gy - 1) / ((double)fld->extent[3] - (double)fld->extent[2]));
+  P.f_half = fld->half_range;
+  P.inv_band = (float)((double)fld->bands / (2.0 * (double)fld->half_range));
+  P.f_alpha = fld->alpha, P.line_hw = fld->line_halfwidth;
+  P.grad_eps = 1e-6f * fld->half_range;
+  hipLaunchKernelGGL(render_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, P);
   return (int)hipGetLastError();
 }

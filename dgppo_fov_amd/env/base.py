@@ -464,7 +464,10 @@ class MultiAgentEnv(ABC):
         uint8 RGBA image (*batch, S, S, 4) on the graph's device, S = size or 10 * dpi (the reference's 10 in figure):
         one HIP launch over (frame, pixel tile) (torch.ops.dgppo.render_frames; DESIGN.md "Rendering" has the pixel
         rule and the layers).  viz_opts={"fov": False} leaves out the FoV wedges LidarOmniTarget draws by default.
-        `out` reuses a contiguous uint8 buffer of that shape.  There is no host path: a CPU graph raises."""
+        `out` reuses a contiguous uint8 buffer of that shape.  There is no host path: a CPU graph raises.
+        viz_opts={"field": FieldLayer} (utils/field.py) draws a scalar field per frame -- hard-edged colour bands and a
+        black zero line -- under every other layer (torch.ops.dgppo.render_frames_field): this project's door to the
+        picture the reference draws for viz_opts["cbf"] / ["Vh"], keys that stay unbuilt here."""
         if self.ENGINE in self._VMAS_ENGINES:
             raise NotImplementedError(f"{type(self).__name__}: rendering the VMAS envs is not built (their reference "
                                       "renderers are separate code)")
@@ -491,7 +494,20 @@ class MultiAgentEnv(ABC):
         elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != states.device:
             raise ValueError(f"render_frames: out must be a uint8 {shape} tensor on {states.device}")
         flags = _lib.RENDER_FOV if viz_opts.get("fov", True) else 0
-        torch.ops.dgppo.render_frames(self._cfg_handle, states, recv, send, ob, out, flags)
+        field = viz_opts.get("field")
+        if field is None:
+            torch.ops.dgppo.render_frames(self._cfg_handle, states, recv, send, ob, out, flags)
+            return out
+        from ..utils.field import FIELD_ALPHA, FieldLayer, palette_tensor
+
+        if not isinstance(field, FieldLayer):
+            raise ValueError(f"render_frames: viz_opts['field'] must be a FieldLayer, got {type(field).__name__}")
+        if tuple(field.values.shape[:-2]) != bs or field.values.device != states.device:
+            raise ValueError(f"render_frames: the field's values must be {bs + ('Gy', 'Gx')} on {states.device}, got "
+                             f"{tuple(field.values.shape)} on {field.values.device}")
+        torch.ops.dgppo.render_frames_field(self._cfg_handle, states, recv, send, ob, field.values,
+                                            palette_tensor(field.bands, states.device), list(field.extent),
+                                            field.half_range, FIELD_ALPHA, self._area_size / 480.0, out, flags)
         return out
 
     def render_video(self, rollout, video_path, Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
@@ -501,7 +517,9 @@ class MultiAgentEnv(ABC):
         (render_frames, in chunks whose device buffer stays within max_frame_bytes) and copied to the host, where
         Pillow draws the header band above the scene (per-component max cost, reward, unsafe agents, kk) and the
         agent indices and encodes an animated GIF at 30 fps.  A `.mp4` suffix is rewritten to `.gif` (no ffmpeg);
-        the path written is returned.  Ta_is_unsafe: (T, n) booleans (test.py: any(cost >= 0))."""
+        the path written is returned.  Ta_is_unsafe: (T, n) booleans (test.py: any(cost >= 0)).
+        viz_opts={"field": FieldLayer} with values (T, Gy, Gx) draws that field under every frame's scene, one
+        half_range for the whole episode, and writes its label centred in the header."""
         import pathlib
 
         try:
@@ -534,8 +552,13 @@ class MultiAgentEnv(ABC):
         except (TypeError, OSError):  # a Pillow without the scalable default font
             font = label_font = ImageFont.load_default()
             lpx = px
+        field = (viz_opts or {}).get("field")
+        if field is not None and (not hasattr(field, "sliced") or tuple(field.values.shape[:-2]) != (T,)):
+            raise ValueError(f"render_video: viz_opts['field'] must be a FieldLayer with values ({T}, Gy, Gx)")
         for t0 in range(0, T, per):
             t1 = min(T, t0 + per)
+            if field is not None:
+                viz_opts = dict(viz_opts, field=field.sliced(slice(t0, t1)))
             sub = self._assemble(g.nodes[episode, t0:t1], g.edges[episode, t0:t1], g.states[episode, t0:t1],
                                  g.receivers[episode, t0:t1], g.senders[episode, t0:t1],
                                  None if ob is None else ob[episode, t0:t1])
@@ -551,6 +574,8 @@ class MultiAgentEnv(ABC):
                     right.append("Unsafe: [" + " ".join(str(i) for i in np.where(unsafe[t])[0]) + "]")  # one line
                 for i, s in enumerate(right):
                     d.text((S - S // 100 - d.textlength(s, font=font), i * px), s, fill="black", font=font)
+                if field is not None and field.label:
+                    d.text(((S - d.textlength(field.label, font=font)) / 2, 0), field.label, fill="black", font=font)
                 for i in range(n):
                     x, y = pos[t, i]
                     if np.isfinite(x) and np.isfinite(y) and 0 <= x <= self._area_size and 0 <= y <= self._area_size:

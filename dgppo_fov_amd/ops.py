@@ -13,6 +13,7 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::env_rollout    dgppo_env_rollout    lax.scan of env.step over T given actions, trainer/utils.py:45-55
   dgppo::env_get_graph  dgppo_env_get_graph  vmap(env.get_graph)  lidar_env/base.py:126-140, 227-271, mpe/base.py:211-241
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
+  dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
   dgppo::gnn_attn_bwd   dgppo_gnn_attn_bwd   its gradient (the jax.grad of update_Vl / update_policy)
   dgppo::gae            dgppo_gae            compute_dec_ocp_gae, algo/utils.py:11-79
@@ -270,15 +271,9 @@ def _env_get_graph_fake(cfg, agent, goal, third, ray_dirs, nodes, edges, states,
     return None
 
 
-@torch.library.custom_op("dgppo::render_frames", mutates_args=("out",))
-def render_frames(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, obstacles: Optional[Tensor],
-                  out: Tensor, flags: int) -> None:
-    """Rasterise the frames of a graph batch: states (B, N, sd) or (B, T, N, sd) with receivers / senders (B[, T], E)
-    int32 and the Lidar obstacle records (B, O, 16) (one set per episode; None for MPE or n_obs == 0) -> out, a
-    contiguous uint8 (B[, T], S, S, 4) RGBA image stack.  The batch strides are free (the (B, T) view of a time-major
-    rollout buffer passes without a copy); the trailing dims must be contiguous.  flags bit 0: FoV wedges."""
-    _lib.require_gpu(states.device, "dgppo::render_frames")
-    _lib.require_gpu(out.device, "dgppo::render_frames")
+def _render_args(states: Tensor, receivers: Tensor, senders: Tensor, obstacles: Optional[Tensor], out: Tensor,
+                 flags: int) -> _lib.RenderArgs:
+    """Check the tensors of a render_frames call and fill its dgppo_render_args."""
     nb = states.dim() - 2
     if nb not in (1, 2) or receivers.dim() != nb + 1 or receivers.shape != senders.shape or \
             receivers.shape[:nb] != states.shape[:nb]:
@@ -305,7 +300,20 @@ def render_frames(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, 
     a.out = _p(out)
     a.n_frames, a.frames_per_episode = frames, (int(states.shape[1]) if nb == 2 else 1)
     a.size, a.flags = int(out.shape[-2]), int(flags)
-    if frames == 0:
+    return a
+
+
+@torch.library.custom_op("dgppo::render_frames", mutates_args=("out",))
+def render_frames(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, obstacles: Optional[Tensor],
+                  out: Tensor, flags: int) -> None:
+    """Rasterise the frames of a graph batch: states (B, N, sd) or (B, T, N, sd) with receivers / senders (B[, T], E)
+    int32 and the Lidar obstacle records (B, O, 16) (one set per episode; None for MPE or n_obs == 0) -> out, a
+    contiguous uint8 (B[, T], S, S, 4) RGBA image stack.  The batch strides are free (the (B, T) view of a time-major
+    rollout buffer passes without a copy); the trailing dims must be contiguous.  flags bit 0: FoV wedges."""
+    _lib.require_gpu(states.device, "dgppo::render_frames")
+    _lib.require_gpu(out.device, "dgppo::render_frames")
+    a = _render_args(states, receivers, senders, obstacles, out, flags)
+    if a.n_frames == 0:
         return
     _lib.check(_lib.load().dgppo_render_frames(ctypes.byref(env_cfg(cfg)), ctypes.byref(a), _stream(states)),
                "dgppo_render_frames")
@@ -313,6 +321,45 @@ def render_frames(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, 
 
 @render_frames.register_fake
 def _render_frames_fake(cfg, states, receivers, senders, obstacles, out, flags) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::render_frames_field", mutates_args=("out",))
+def render_frames_field(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, obstacles: Optional[Tensor],
+                        values: Tensor, palette: Tensor, extent: List[float], half_range: float, alpha: float,
+                        line_halfwidth: float, out: Tensor, flags: int) -> None:
+    """render_frames with a scalar field under every other layer: values, contiguous float32 (B[, T], Gy, Gx) on the
+    states' device, one grid per frame on the uniform axes spanning extent = (x0, x1, y0, y1); palette, contiguous
+    float32 (K, 3) straight sRGB on that device, K bands over [-half_range, half_range]; alpha of the bands on white;
+    the black zero line's half-width in world units.  DESIGN.md "Rendering" has the pixel rule."""
+    _lib.require_gpu(states.device, "dgppo::render_frames_field")
+    _lib.require_gpu(out.device, "dgppo::render_frames_field")
+    a = _render_args(states, receivers, senders, obstacles, out, flags)
+    nb = states.dim() - 2
+    if values.dtype != torch.float32 or values.dim() != nb + 2 or values.shape[:nb] != states.shape[:nb] or \
+            not values.is_contiguous() or values.device != states.device:
+        raise ValueError("render_frames_field: values must be a contiguous float32 (B[, T], Gy, Gx) tensor on the "
+                         "states' device")
+    if palette.dtype != torch.float32 or palette.dim() != 2 or palette.shape[1] != 3 or not palette.is_contiguous() or \
+            palette.device != states.device:
+        raise ValueError("render_frames_field: palette must be a contiguous float32 (K, 3) tensor on the states' "
+                         "device")
+    if len(extent) != 4:
+        raise ValueError("render_frames_field: extent is (x0, x1, y0, y1)")
+    f = _lib.RenderField()
+    f.values, f.palette = _p(values), _p(palette)
+    f.gy, f.gx, f.bands = int(values.shape[-2]), int(values.shape[-1]), int(palette.shape[0])
+    f.extent[:] = [float(v) for v in extent]
+    f.half_range, f.alpha, f.line_halfwidth = float(half_range), float(alpha), float(line_halfwidth)
+    if a.n_frames == 0:
+        return
+    _lib.check(_lib.load().dgppo_render_frames_field(ctypes.byref(env_cfg(cfg)), ctypes.byref(a), ctypes.byref(f),
+                                                     _stream(states)), "dgppo_render_frames_field")
+
+
+@render_frames_field.register_fake
+def _render_frames_field_fake(cfg, states, receivers, senders, obstacles, values, palette, extent, half_range, alpha,
+                              line_halfwidth, out, flags) -> None:
     return None
 
 

@@ -241,6 +241,31 @@ typedef struct dgppo_render_args {
 
 int dgppo_render_frames(const dgppo_env_cfg* cfg, const dgppo_render_args* a, void* stream);
 
+/* dgppo_render_frames with a scalar field drawn under every other layer (layer 0): the reference's contourf + black
+ * zero-level contour (plot.py viz_opts["cbf"], :348-372, 608-705) by this project's own rule (DESIGN.md "Rendering").
+ * Frame f reads the (gy, gx) float32 nodes at values + f * gy * gx, node (j, i) at (extent[0] + i dx, extent[2] +
+ * j dy), extent = (x0, x1, y0, y1), dx = (x1 - x0) / (gx - 1).  A pixel centre inside the extent interpolates its
+ * cell bilinearly, takes band clamp(floor((val + half_range) / (2 half_range) * bands), 0, bands - 1) of `palette`
+ * (device, (bands, 3) straight sRGB floats) at `alpha` on white, then the black zero line of half-width
+ * `line_halfwidth` (world units) around val = 0.  A pixel outside the extent or in a cell with a non-finite node is
+ * not painted.  `field` NULL: exactly dgppo_render_frames.
+ * DGPPO_EINVAL: what dgppo_render_frames rejects; a NULL values / palette; gx or gy < 2; bands outside
+ * [2, DGPPO_RENDER_MAX_BANDS]; a non-finite or empty extent; half_range not finite or <= 0; alpha outside [0, 1];
+ * a negative or non-finite line_halfwidth; `out` overlapping values or palette. */
+#define DGPPO_RENDER_MAX_BANDS 32
+typedef struct dgppo_render_field {
+  const float* values;
+  int32_t gx, gy;
+  float extent[4];
+  float half_range;
+  int32_t bands;
+  const float* palette;
+  float alpha, line_halfwidth;
+} dgppo_render_field;
+
+int dgppo_render_frames_field(const dgppo_env_cfg* cfg, const dgppo_render_args* a, const dgppo_render_field* field,
+                              void* stream);
+
 /* T env steps with given actions in one call: replaces the env half of the reference's rollout scan
  * `lax.scan(body, ...)` over env.step (dgppo/trainer/utils.py:45-55) for a fixed action sequence.
  * `step` describes graph 0 and step 0: graph t's rows live at the graph pointers + t * t_<field>

@@ -16,6 +16,11 @@ names with .gif for .mp4 (no ffmpeg).  The reference renders every episode unles
 default is no video, so a 1000-episode evaluation does not encode 1000 GIFs, and --no-video stays accepted (it wins
 over --video).  The metric lines are the same with and without --video.
 
+`--cbf AGENT` (with --video) draws the learned safety value under each rendered episode: h = -max over the cost
+components of Vh, had agent AGENT stood at each node of a `--cbf-grid` G x G grid (default 32) with everything else
+and the carry fixed (utils/field.py value_field).  Red is predicted unsafe, blue safe, the black line the boundary of
+the learned safe set.  It needs an algorithm with get_Vh (dgppo, hcbfcrpo).
+
 Beyond the reference: `--scene PATH` evaluates on the initial states stored in a scene file
 (dgppo_fov_amd/utils/scene.py) instead of seeds -- episodes are rows [offset:epi] of the file, all of its rows when
 --epi is not given -- and `--dump-scene PATH` writes the initial states of the episodes that ran, so
@@ -57,6 +62,13 @@ def test(args):
                      max_grad_norm=2.0, seed=cfg["seed"], use_rnn=cfg.get("use_rnn", True),
                      rnn_layers=cfg.get("rnn_layers", 1), use_lstm=cfg.get("use_lstm", False),
                      batch_size=cfg.get("batch_size", 16384), rnn_step=cfg.get("rnn_step", 16), device=dev)
+    if args.cbf is not None and args.video and not args.no_video:  # refused before anything is loaded or run
+        if not callable(getattr(algo, "get_Vh", None)):
+            raise SystemExit(f"--cbf needs an algorithm with get_Vh; {cfg['algo']} has none")
+        if not 0 <= args.cbf < env.num_agents:
+            raise SystemExit(f"--cbf {args.cbf} is not an agent index in [0, {env.num_agents})")
+        if args.cbf_grid < 2:
+            raise SystemExit(f"--cbf-grid {args.cbf_grid} < 2")
     model_path = os.path.join(args.path, "models")
     step = args.step if args.step is not None else max(int(d) for d in os.listdir(model_path) if d.isdigit())
     print("step: ", step)
@@ -114,8 +126,15 @@ def test(args):
         for k, i in list(enumerate(episodes))[:max(args.max_videos, 0)]:
             rate = (1 - is_unsafe[k].mean()) * 100
             name = f"n{num_agents}_epi{i:02}_reward{rewards[k]:.3f}_cost{costs[k]:.3f}_sr{rate:.0f}"
-            env.render_video(roll, os.path.join(videos_dir, f"{stamp}_{name}.gif"), Ta_is_unsafe[k], {}, dpi=args.dpi,
-                             episode=k)
+            viz_opts = {}
+            if args.cbf is not None:
+                from dgppo_fov_amd.utils.field import FieldLayer, grid_axes, value_field
+
+                xs, ys = grid_axes(env, args.cbf_grid)
+                h = -value_field(algo, roll, k, args.cbf, xs, ys).amax(dim=-1)  # (T, G, G)
+                viz_opts["field"] = FieldLayer.centred(h.contiguous(), xs, ys, f"h = -max Vh, agent {args.cbf}")
+            env.render_video(roll, os.path.join(videos_dir, f"{stamp}_{name}.gif"), Ta_is_unsafe[k], viz_opts,
+                             dpi=args.dpi, episode=k)
     return dict(reward=float(np.mean(rewards)), cost=float(np.mean(costs)), safe_rate=float(safe_mean))
 
 
@@ -141,6 +160,8 @@ def main():
     parser.add_argument("--env", type=str, default=None)
     parser.add_argument("--offset", type=int, default=0)
     parser.add_argument("--dpi", type=int, default=100)
+    parser.add_argument("--cbf", type=int, default=None, metavar="AGENT")  # with --video: the Vh field of this agent
+    parser.add_argument("--cbf-grid", type=int, default=32, metavar="G")
     return test(parser.parse_args())
 
 
