@@ -124,6 +124,11 @@ class _Opt:
 
 class DGPPO:
     VH_NET = VhNet  # the cost critic's network class (InforMARL-Lagr: VhGlobalNet)
+    NETS = ("Vl", "Vh", "policy")  # the nets the minibatch step trains, in grad_flat order
+    # the minibatch step's passes on concurrent streams (policy, Vl, Vh) over a prepared GraphBatch, weight gradients
+    # deferred, one multi-net Adam, hipGraph replay; False (the baselines): one pass after another on the current
+    # stream (Vl, Vh, policy), a GEMM per weight gradient, one Adam step per net
+    CONCURRENT = True
 
     def __init__(self, env: MultiAgentEnv, node_dim: int, edge_dim: int, state_dim: int, action_dim: int,
                  n_agents: int, actor_gnn_layers: int = 2, Vl_gnn_layers: int = 2, Vh_gnn_layers: int = 1,
@@ -162,15 +167,15 @@ class DGPPO:
                               edge_dim=edge_dim, **rk)
         self.n_carries = self.actor.gru.carries
         # one flat gradient buffer for the three nets (one all-reduce per minibatch)
-        sizes = [self.Vl.ps.size, self.Vh.ps.size, self.actor.ps.size]
-        self.grad_flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+        self.nets = {"Vl": self.Vl, "Vh": self.Vh, "policy": self.actor}
+        self.grad_flat = torch.zeros(sum(net.ps.size for net in self.nets.values()), dtype=torch.float32, device=dev)
         off = 0
-        for net, sz in zip((self.Vl, self.Vh, self.actor), sizes):
-            net.ps.grad = self.grad_flat[off:off + sz]
+        for net in self.nets.values():
+            net.ps.grad = self.grad_flat[off:off + net.ps.size]
             net.ps.build_views()
-            off += sz
-        self.opt = {"Vl": _Opt(self.Vl.ps, lr_Vl, max_grad_norm, dev), "Vh": _Opt(self.Vh.ps, lr_Vh, max_grad_norm, dev),
-                    "policy": _Opt(self.actor.ps, lr_actor, max_grad_norm, dev)}
+            off += net.ps.size
+        self.opt = {name: _Opt(self.nets[name].ps, lr, max_grad_norm, dev)
+                    for name, lr in (("Vl", lr_Vl), ("Vh", lr_Vh), ("policy", lr_actor))}
         # the reference draws the entropy's tanh-Jacobian sample ONCE at trace time with a fixed key,
         # identical for every vmapped env/step (distribution.py:37-43); here: a fixed (n, A) draw
         self.entropy_eps = torch.from_numpy(
@@ -332,28 +337,32 @@ class DGPPO:
         return out
 
     def _graph_batch(self, nodes, edges, recv, send) -> GraphBatch:
-        Be, T = nodes.shape[:2]
-        return GraphBatch(nodes.view(Be * T, *nodes.shape[2:]), edges.view(Be * T, *edges.shape[2:]),
-                          recv.view(Be * T, -1), send.view(Be * T, -1), self._n_agents,
-                          self._env.agent_candidates(self.device), raw_cols=self._env.nonagent_feature_cols)
+        return GraphBatch.of(self._env, nodes, edges, recv, send)
 
     def _graphs(self, graph, envs) -> GraphBatch:
-        """(Be, T, ...) graphs of the selected envs, env-major -> contiguous GraphBatch."""
-        if not isinstance(envs, slice):
-            return self._graph_batch(*self._gather(envs, graph.nodes, graph.edges, graph.receivers, graph.senders))
-        sel = lambda x: x[envs]  # noqa: E731
-        nodes, edges = sel(graph.nodes).contiguous(), sel(graph.edges).contiguous()
-        recv, send = sel(graph.receivers).contiguous(), sel(graph.senders).contiguous()
-        Be, T = nodes.shape[:2]
-        return GraphBatch(nodes.view(Be * T, *nodes.shape[2:]), edges.view(Be * T, *edges.shape[2:]),
-                          recv.view(Be * T, -1), send.view(Be * T, -1), self._n_agents,
-                          self._env.agent_candidates(self.device), raw_cols=self._env.nonagent_feature_cols)
+        """(Be, T, ...) graphs of the selected envs (a slice or an index tensor), env-major -> contiguous GraphBatch."""
+        f = (graph.nodes, graph.edges, graph.receivers, graph.senders)
+        return self._graph_batch(*([x[envs] for x in f] if isinstance(envs, slice) else self._gather(envs, *f)))
 
     def _last_graph(self, next_graph, envs=slice(None)) -> GraphBatch:
         ng = next_graph
-        return GraphBatch(ng.nodes[envs, -1], ng.edges[envs, -1], ng.receivers[envs, -1], ng.senders[envs, -1],
-                          self._n_agents, self._env.agent_candidates(self.device),
-                          raw_cols=self._env.nonagent_feature_cols)
+        return self._graph_batch(ng.nodes[envs, -1], ng.edges[envs, -1], ng.receivers[envs, -1], ng.senders[envs, -1])
+
+    def _time_major(self, rollout: Rollout, chunk: int):
+        """The rollout's graphs in whole time steps, about `chunk` envs' worth at a time, read in place from the
+        RolloutEngine's time-major buffers: yields (t0, t1, GraphBatch of the (t1 - t0) * B graphs, their carry rows
+        (t1 - t0, B, n, W)).  For passes whose graphs are independent.  Yields nothing when the Rollout is not the
+        engine's (B, T) view of (T, B) buffers; the caller then copies env chunks."""
+        g = rollout.graph
+        f = [x.transpose(0, 1) for x in (g.nodes, g.edges, g.receivers, g.senders)]
+        h = self._rows(rollout.rnn_states).transpose(0, 1)
+        if not all(x.is_contiguous() for x in f + [h]):
+            return
+        T, B = h.shape[:2]
+        tc = max(1, (chunk * T) // B)
+        for t0 in range(0, T, tc):
+            t1 = min(T, t0 + tc)
+            yield t0, t1, self._graph_batch(*(x[t0:t1] for x in f)), h[t0:t1]
 
     def _vl_all(self, rollout: Rollout, chunk: int) -> torch.Tensor:
         """scan_Vl over every env's whole episode from the zero carry, plus the final Vl at next_graph[:, -1]
@@ -361,47 +370,30 @@ class DGPPO:
         B, T = rollout.rewards.shape
         Vl = torch.empty((B, T + 1), device=self.device)
         hT_all = torch.empty((B, self.Vl.carry_width), device=self.device)
-        tm = self._time_major(rollout, self._rows) if hasattr(self.Vl, "graph_means") else None
-        if tm is not None:
-            # the GNN + agent mean over the time-major graphs in place (whole time steps per chunk; graphs are
-            # independent), then head + GRU scan per env sequence from the (B, T, 64) means: bit-identical to
-            # env-chunked graph copies, without copying the graphs
-            (nodes, edges, recv, send), _ = tm
-            zm = torch.empty((T, B, 64), device=self.device)
-            tc = max(1, (chunk * T) // B)
-            for t0 in range(0, T, tc):
-                t1 = min(T, t0 + tc)
-                G = (t1 - t0) * B
-                g = GraphBatch(nodes[t0:t1].reshape(G, *nodes.shape[2:]), edges[t0:t1].reshape(G, *edges.shape[2:]),
-                               recv[t0:t1].reshape(G, -1), send[t0:t1].reshape(G, -1), self._n_agents,
-                               self._env.agent_candidates(self.device), raw_cols=self._env.nonagent_feature_cols)
-                self.Vl.graph_means(g, out=zm[t0:t1].view(G, 64))
+        # the GNN + agent mean over the time-major graphs in place (graphs are independent), then head + GRU scan per
+        # env sequence from the (B, T, 64) means: bit-identical to env-chunked graph copies, without copying the graphs
+        zm = None
+        for t0, t1, g, _ in self._time_major(rollout, chunk):
+            zm = torch.empty((T, B, 64), device=self.device) if zm is None else zm
+            self.Vl.graph_means(g, out=zm[t0:t1].view(g.G, 64))
+        if zm is not None:
             zm_env = zm.transpose(0, 1).contiguous()  # (B, T, 64): rows e * T + t
             # head + GRU scan of every env in ONE pass (rows independent: bit-identical to env chunks); chunks of
             # 512 envs left the scan's 128 dependent steps on 32 workgroups, one chunk after another
             v, hT, _ = self.Vl.seq_fwd(None, B, T, keep_cache=False, zm=zm_env.view(-1, 64))
             Vl[:, :T].copy_(v)
             hT_all.copy_(hT)
-        for e0 in range(0, B, chunk) if tm is None else ():
-            e1 = min(B, e0 + chunk)
-            g = self._graphs(rollout.graph, slice(e0, e1))
-            v, hT, _ = self.Vl.seq_fwd(g, e1 - e0, T, keep_cache=False)
-            Vl[e0:e1, :T].copy_(v)
-            hT_all[e0:e1].copy_(hT)
+        else:
+            for e0 in range(0, B, chunk):
+                e1 = min(B, e0 + chunk)
+                g = self._graphs(rollout.graph, slice(e0, e1))
+                v, hT, _ = self.Vl.seq_fwd(g, e1 - e0, T, keep_cache=False)
+                Vl[e0:e1, :T].copy_(v)
+                hT_all[e0:e1].copy_(hT)
         # the final values of every env in one pass (rows are independent: identical to per-chunk passes)
         vf, _, _ = self.Vl.seq_fwd(self._last_graph(rollout.next_graph), B, 1, h0=hT_all, keep_cache=False)
         Vl[:, T].copy_(vf[:, 0])
         return Vl
-
-    @staticmethod
-    def _time_major(rollout: Rollout, rows_fn):
-        """(T, B, ...) contiguous views of the rollout's graph fields and carry rows when the Rollout is the
-        RolloutEngine's (B, T) view of its time-major buffers (else None): passes whose graphs are independent
-        (Vh: one GRU step per graph) then read the buffers in place instead of copying env chunks."""
-        g = rollout.graph
-        f = [x.transpose(0, 1) for x in (g.nodes, g.edges, g.receivers, g.senders)]
-        h = rows_fn(rollout.rnn_states).transpose(0, 1)
-        return (f, h) if all(x.is_contiguous() for x in f + [h]) else None
 
     def _vh_all(self, rollout: Rollout, chunk: int):
         """Vh on every (env, t) graph with the stored actor carries, plus the final Vh (dgppo.py:218-228).  Graphs
@@ -409,24 +401,18 @@ class DGPPO:
         (bit-identical to env chunks: no reduction crosses graphs)."""
         B, T, n = rollout.rewards.shape[0], rollout.rewards.shape[1], self._n_agents
         out = torch.empty((B, T + 1, n, self._env.n_cost), device=self.device)
-        tm = self._time_major(rollout, self._rows)
-        if tm is not None:
-            (nodes, edges, recv, send), hrows = tm
-            tc = max(1, (chunk * T) // B)
-            for t0 in range(0, T, tc):
-                t1 = min(T, t0 + tc)
-                G = (t1 - t0) * B
-                g = GraphBatch(nodes[t0:t1].reshape(G, *nodes.shape[2:]), edges[t0:t1].reshape(G, *edges.shape[2:]),
-                               recv[t0:t1].reshape(G, -1), send[t0:t1].reshape(G, -1), n,
-                               self._env.agent_candidates(self.device), raw_cols=self._env.nonagent_feature_cols)
-                v, _ = self.Vh.fwd(g, hrows[t0:t1].reshape(G * n, -1), keep_cache=False)
-                out[:, t0:t1].copy_(v.view(t1 - t0, B, n, -1).transpose(0, 1))
-        for e0 in range(0, B, chunk) if tm is None else ():
-            e1 = min(B, e0 + chunk)
-            g = self._graphs(rollout.graph, slice(e0, e1))
-            h = self._rows(rollout.rnn_states[e0:e1]).reshape((e1 - e0) * T * n, -1).contiguous()
-            v, _ = self.Vh.fwd(g, h, keep_cache=False)
-            out[e0:e1, :T].copy_(v.view(e1 - e0, T, n, -1))
+        in_place = False
+        for t0, t1, g, h in self._time_major(rollout, chunk):
+            in_place = True
+            v, _ = self.Vh.fwd(g, h.reshape(g.G * n, -1), keep_cache=False)
+            out[:, t0:t1].copy_(v.view(t1 - t0, B, n, -1).transpose(0, 1))
+        if not in_place:
+            for e0 in range(0, B, chunk):
+                e1 = min(B, e0 + chunk)
+                g = self._graphs(rollout.graph, slice(e0, e1))
+                h = self._rows(rollout.rnn_states[e0:e1]).reshape((e1 - e0) * T * n, -1).contiguous()
+                v, _ = self.Vh.fwd(g, h, keep_cache=False)
+                out[e0:e1, :T].copy_(v.view(e1 - e0, T, n, -1))
         # final, every env in one pass: act on next_graph[-1] from rnn_states[-1], then Vh with that carry
         gl = self._last_graph(rollout.next_graph)
         h_last = self._rows(rollout.rnn_states[:, -1]).reshape(B * n, -1).contiguous()
@@ -552,87 +538,115 @@ class DGPPO:
         return out
 
     def _mb_apply(self):
-        """clip + finite check + Adam of the three nets: two launches for all three (dgppo_adam_multi, bit-identical
-        to the per-net grad_norm + adam pairs; DGPPO_ADAM_MULTI=0 runs the pairs)."""
-        names = ("Vl", "Vh", "policy")
-        if ADAM_MULTI() and self.device.type == "cuda":
+        """clip + finite check + Adam of the trained nets (NETS).  CONCURRENT: two launches for all of them
+        (dgppo_adam_multi, bit-identical to the per-net grad_norm + adam pairs; DGPPO_ADAM_MULTI=0 runs the pairs)."""
+        if self.CONCURRENT and ADAM_MULTI() and self.device.type == "cuda":
             K.adam_multi([(o.ps.flat, o.ps.grad, o.m, o.v, o.state, o.lr, o.max_norm)
-                          for o in (self.opt[k] for k in names)])
+                          for o in (self.opt[k] for k in self.NETS)])
             return
-        for name in names:
+        for name in self.NETS:
             self.opt[name].step()
+
+    def _minibatches(self, B: int, T: int):
+        """One PPO epoch's minibatches of this rank (dgppo.py:155-159): yields (env indices, the same on the device)."""
+        assert T % self.rnn_step == 0, "jnp.array(jnp.array_split(...)) in the reference needs rnn_step | T"
+        batches = minibatch_plan(B, T, self.world, self.batch_size, self.np_rng)
+        return zip(batches, self._env_ids(batches))
+
+    def _mb_rows(self, envs, graph, *fields):
+        """The minibatch's rows (x[idx] of dgppo.py:278-279): the selected envs' graphs as one GraphBatch (its derived
+        tables built now when concurrent passes will read it) and their (len(envs), T, ...) copies of `fields`."""
+        nodes, edges, recv, send, *rest = self._gather(envs, graph.nodes, graph.edges, graph.receivers, graph.senders,
+                                                       *fields)
+        g = self._graph_batch(nodes, edges, recv, send)
+        return (g.prepare() if self.CONCURRENT else g, *rest)
+
+    def _wgrad(self, net):
+        return K.defer_wgrad(self.device, net.ps.grad, self.CONCURRENT and DEFER_WGRAD())
+
+    def _vl_pass(self, g, tgt, S, L, ph, pending):
+        """update_Vl (informarl.py:357-385): l2 to tgt (S, L) over S sequences of L graphs from zero carries."""
+        v, _, cache = self.Vl.seq_fwd(g, S, L)
+        dv = torch.empty_like(v)
+        loss = torch.empty(1, device=self.device)
+        K.l2_loss(v, tgt, dv, loss)
+        ph.mark("Vl_fwd")
+        with self._wgrad(self.Vl):
+            self.Vl.seq_bwd(cache, dv)
+        self._start_reduce(self.Vl, pending)  # the bucket's all-reduce overlaps the other passes
+        ph.mark("Vl_bwd")
+        return loss
+
+    def _vh_pass(self, g, tgt, S, L, ph, pending, h=None):
+        """update_Vh (dgppo.py:296-321) on the deterministic rollout: l2 to tgt (rows, n_cost), every graph one step
+        from its stored actor carry h (S graphs, L = 1)."""
+        vh, cache = self.Vh.fwd(g, h)
+        dvh = torch.empty_like(vh)
+        loss = torch.empty(1, device=self.device)
+        K.l2_loss(vh, tgt, dvh, loss)
+        ph.mark("Vh_fwd")
+        with self._wgrad(self.Vh):
+            self.Vh.bwd(cache, dvh)
+        self._start_reduce(self.Vh, pending)
+        ph.mark("Vh_bwd")
+        return loss
+
+    def _pi_pass(self, g, acts, lp_old, adv, S, L, ph, pending):
+        """update_policy (informarl.py:405-457): the clipped PPO + entropy statistics (4,)."""
+        lp, ent, cache = self.actor.eval_seq_fwd(g, S, L, acts, self.entropy_eps)
+        dlp = torch.empty_like(lp)
+        dent = torch.empty_like(ent)
+        st = torch.empty(4, device=self.device)
+        K.ppo_loss(lp, lp_old, adv, ent, self.clip_eps, self.coef_ent, dlp, dent, st)
+        ph.mark("pi_fwd")
+        with self._wgrad(self.actor):
+            self.actor.eval_seq_bwd(cache, dlp, dent)
+        self._start_reduce(self.actor, pending)
+        ph.mark("pi_bwd")
+        return st
+
+    def _mb_step(self, jobs, ph, apply=True):
+        """The minibatch step around its gradient passes: run `jobs` (closures over the pass helpers taking the pending
+        all-reduce list; they write disjoint slices of the zeroed grad_flat), finish the gradient all-reduce, record
+        the parity trace, clip + finite check + Adam.  CONCURRENT: the jobs on concurrent streams, else one after
+        another, each pass's cache released when its helper returns.  apply=False (graph capture): the jobs only.
+        Returns the jobs' results."""
+        pending = []
+        calls = [lambda job=job: job(pending) for job in jobs]
+        out = self._parallel(calls) if self.CONCURRENT else [call() for call in calls]
+        if not apply:  # the caller all-reduces and runs clip + Adam from a second graph
+            return out
+        # gradient buckets all-reduced (sum, then / world), clip + finite check + Adam per net
+        self._finish_reduce(pending)
+        if self.trace is not None:
+            snap = lambda f: {k: f(o).clone() for k, o in self.opt.items()}  # noqa: E731
+            self.trace.setdefault("mb", []).append(dict(
+                grad=self.grad_flat.clone(), before=snap(lambda o: o.ps.flat), m_before=snap(lambda o: o.m),
+                v_before=snap(lambda o: o.v), state_before=snap(lambda o: o.state)))
+        self._mb_apply()
+        ph.mark("allreduce_adam")
+        return out
+
+    def _trace_mb(self, bi, **tensors):
+        """Complete the minibatch's trace entry: its env indices and the given losses / statistics (cloned)."""
+        if self.trace is not None:
+            self.trace["mb"][-1].update(envs=bi.copy(), **{k: v.clone() for k, v in tensors.items()})
 
     def _mb_body(self, envs, rollout, det, A, Ql, Qh_det, Bm, T, L, ph, apply=True):
         """One minibatch (dgppo.py:275-289): gradients of Vl, Vh and the policy on the minibatch's envs, then
         clip + finite check + Adam per net.  Device work only (capturable)."""
-        env, dev, n = self._env, self.device, self._n_agents
-        S_per_env = T // L
-        if self.trace is not None:
-            self._mb_before = dict(p={k: o.ps.flat.clone() for k, o in self.opt.items()},
-                                   m={k: o.m.clone() for k, o in self.opt.items()},
-                                   v={k: o.v.clone() for k, o in self.opt.items()},
-                                   s={k: o.state.clone() for k, o in self.opt.items()})
+        S = Bm * (T // L)
         self.grad_flat.zero_()
-        # the minibatch's rows of both rollouts (x[idx] of dgppo.py:278-279): two gather launches
-        rg = rollout.graph
-        nodes, edges, recv, send, acts, lp_old, adv, tgt = self._gather(
-            envs, rg.nodes, rg.edges, rg.receivers, rg.senders, rollout.actions, rollout.log_pis, A, Ql)
-        g = self._graph_batch(nodes, edges, recv, send).prepare()
-        dg = det.graph
-        dnodes, dedges, drecv, dsend, hd, qhd = self._gather(
-            envs, dg.nodes, dg.edges, dg.receivers, dg.senders, self._rows(det.rnn_states), Qh_det)
-        gd = self._graph_batch(dnodes, dedges, drecv, dsend).prepare()
-        tgt = tgt.view(Bm * S_per_env, L)
+        # the minibatch's rows of both rollouts: two gather launches
+        g, acts, lp_old, adv, tgt = self._mb_rows(envs, rollout.graph, rollout.actions, rollout.log_pis, A, Ql)
+        gd, hd, qhd = self._mb_rows(envs, det.graph, self._rows(det.rnn_states), Qh_det)
+        tgt, hd, qhd = tgt.view(S, L), hd.view(Bm * T * self._n_agents, -1), qhd.view(-1, self._env.n_cost)
         acts, lp_old, adv = acts.view(-1, self._action_dim), lp_old.view(-1), adv.view(-1)
-        pending = []
-
-        def vl_job():  # update_Vl (informarl.py:357-385)
-            v, _, cache = self.Vl.seq_fwd(g, Bm * S_per_env, L)
-            dv = torch.empty_like(v)
-            loss = torch.empty(1, device=dev)
-            K.l2_loss(v, tgt, dv, loss)
-            ph.mark("Vl_fwd")
-            with K.defer_wgrad(dev, self.Vl.ps.grad, DEFER_WGRAD()):
-                self.Vl.seq_bwd(cache, dv)
-            self._start_reduce(self.Vl, pending)  # the bucket's all-reduce overlaps the other passes
-            ph.mark("Vl_bwd")
-            return loss
-
-        def vh_job():  # update_Vh (dgppo.py:296-321) on the deterministic rollout
-            vh, cache = self.Vh.fwd(gd, hd.view(Bm * T * n, -1))
-            dvh = torch.empty_like(vh)
-            loss = torch.empty(1, device=dev)
-            K.l2_loss(vh, qhd.view(-1, env.n_cost), dvh, loss)
-            ph.mark("Vh_fwd")
-            with K.defer_wgrad(dev, self.Vh.ps.grad, DEFER_WGRAD()):
-                self.Vh.bwd(cache, dvh)
-            self._start_reduce(self.Vh, pending)
-            ph.mark("Vh_bwd")
-            return loss
-
-        def pi_job():  # update_policy (informarl.py:405-457)
-            lp, ent, cache = self.actor.eval_seq_fwd(g, Bm * S_per_env, L, acts, self.entropy_eps)
-            dlp = torch.empty_like(lp)
-            dent = torch.empty_like(ent)
-            st = torch.empty(4, device=dev)
-            K.ppo_loss(lp, lp_old, adv, ent, self.clip_eps, self.coef_ent, dlp, dent, st)
-            ph.mark("pi_fwd")
-            with K.defer_wgrad(dev, self.actor.ps.grad, DEFER_WGRAD()):
-                self.actor.eval_seq_bwd(cache, dlp, dent)
-            self._start_reduce(self.actor, pending)
-            ph.mark("pi_bwd")
-            return st
-
         # the three passes are independent (own parameters and gradient slices): concurrent streams
-        stats, vl_loss, vh_loss = self._parallel([pi_job, vl_job, vh_job])
-        if not apply:  # graph capture: the caller all-reduces and runs clip + Adam from a second graph
-            return vl_loss, vh_loss, stats, tgt, lp_old
-        # gradient buckets all-reduced (sum, then / world), clip + finite check + Adam per net
-        self._finish_reduce(pending)
-        if self.trace is not None:
-            self._mb_grad = self.grad_flat.clone()
-        self._mb_apply()
-        ph.mark("allreduce_adam")
+        stats, vl_loss, vh_loss = self._mb_step([
+            lambda pending: self._pi_pass(g, acts, lp_old, adv, S, L, ph, pending),
+            lambda pending: self._vl_pass(g, tgt, S, L, ph, pending),
+            lambda pending: self._vh_pass(gd, qhd, Bm * T, 1, ph, pending, h=hd)], ph, apply)
         return vl_loss, vh_loss, stats, tgt, lp_old
 
     def update(self, rollout: Rollout, step: int) -> dict:
@@ -691,15 +705,11 @@ class DGPPO:
                                   Qh=Qh.clone(), Qh_det=Qh_det.clone(), A=A.clone(), safe_cnt=safe_cnt.clone(),
                                   mb=[])
             # ---- minibatches (dgppo.py:155-159, 275-289)
-            batches = minibatch_plan(B, T, self.world, self.batch_size, self.np_rng)
-            L = self.rnn_step
-            assert T % L == 0, "jnp.array(jnp.array_split(...)) in the reference needs rnn_step | T"
-            env_ids = self._env_ids(batches)
-            graph_ok = self._mb_graph_ok(batches, ph, T)
+            mbs = list(self._minibatches(B, T))
+            graph_ok = self._mb_graph_ok([bi for bi, _ in mbs], ph, T)
             self._flat_reduce = graph_ok
-            for k, bi in enumerate(batches):
-                envs = next(env_ids)
-                args = (rollout, det, A, Ql, Qh_det, len(bi), T, L)
+            for bi, envs in mbs:
+                args = (rollout, det, A, Ql, Qh_det, len(bi), T, self.rnn_step)
                 if graph_ok:
                     gkey = self._mb_graph_key(*args)
                     if self._mbg is not None and self._mbg[0] == gkey:
@@ -710,11 +720,7 @@ class DGPPO:
                 else:
                     out = self._mb_body(envs, *args, ph)
                 vl_loss, vh_loss, stats, tgt, lp_old = out
-                if self.trace is not None:
-                    self.trace["mb"].append(dict(
-                        envs=bi.copy(), grad=self._mb_grad, vl_loss=vl_loss.clone(), vh_loss=vh_loss.clone(),
-                        stats=stats.clone(), before=self._mb_before["p"], m_before=self._mb_before["m"],
-                        v_before=self._mb_before["v"], state_before=self._mb_before["s"]))
+                self._trace_mb(bi, vl_loss=vl_loss, vh_loss=vh_loss, stats=stats)
             self._flat_reduce = False
             info = {"Vl/loss": vl_loss, "Vl/max_target": tgt.max(), "Vl/min_target": tgt.min(),
                     "Vh/loss_Vh": vh_loss, "policy/stats": stats, "policy/log_pi_min": lp_old.min()}
@@ -758,14 +764,18 @@ class DGPPO:
         return out
 
     # ---- checkpoints ---------------------------------------------------------------------------
+    def _ckpt_files(self, d: str):
+        """(file, net, optimiser) of every net's checkpoint under d: {actor,Vl,Vh}.pt."""
+        return [(os.path.join(d, ("actor" if name == "policy" else name) + ".pt"), net, self.opt[name])
+                for name, net in self.nets.items()]
+
     def save(self, save_dir: str, step: int):
         """models/<step>/{actor,Vl,Vh}.pt: params AND Adam state (the reference keeps params only)."""
         d = os.path.join(save_dir, str(step))
         os.makedirs(d, exist_ok=True)
-        for name, net, opt in (("actor", self.actor, self.opt["policy"]), ("Vl", self.Vl, self.opt["Vl"]),
-                               ("Vh", self.Vh, self.opt["Vh"])):
+        for fn, net, opt in self._ckpt_files(d):
             torch.save({"params": net.ps.flat.cpu(), "m": opt.m.cpu(), "v": opt.v.cpu(), "state": opt.state.cpu(),
-                        "layout": [(n, s) for n, s, _ in net.ps.entries]}, os.path.join(d, f"{name}.pt"))
+                        "layout": [(n, s) for n, s, _ in net.ps.entries]}, fn)
 
     def load(self, load_dir: str, step: int):
         """models/<step>/{actor,Vl,Vh}.pt of this package, or reference-layout {actor,Vl,Vh}.npz flax
@@ -776,8 +786,7 @@ class DGPPO:
 
             load_reference_npz(self, d)
             return
-        for name, net, opt in (("actor", self.actor, self.opt["policy"]), ("Vl", self.Vl, self.opt["Vl"]),
-                               ("Vh", self.Vh, self.opt["Vh"])):
-            ck = torch.load(os.path.join(d, f"{name}.pt"), weights_only=True)
+        for fn, net, opt in self._ckpt_files(d):
+            ck = torch.load(fn, weights_only=True)
             net.ps.flat.copy_(ck["params"])
             opt.m.copy_(ck["m"]), opt.v.copy_(ck["v"]), opt.state.copy_(ck["state"])

@@ -16,10 +16,13 @@ import torch
 
 from ..nn import kernels as K
 from ..trainer.rollout import Rollout
-from .dgppo import PREPASS_GRAPHS, DGPPO, minibatch_plan
+from .dgppo import PREPASS_GRAPHS, DGPPO, _Phases
 
 
 class InforMARL(DGPPO):
+    NETS = ("Vl", "policy")  # Vh's parameters and Adam state stay as built (they are in the checkpoints)
+    CONCURRENT = False
+
     def __init__(self, *args, cost_weight: float = 0.0, cost_schedule: bool = False, **kwargs):
         super().__init__(*args, **kwargs)
         self.cost_weight, self.cost_schedule = float(cost_weight), bool(cost_schedule)
@@ -68,50 +71,32 @@ class InforMARL(DGPPO):
         return Ql, A, {}
 
     def update(self, rollout: Rollout, step: int) -> dict:
-        dev = self.device
         B, T = rollout.rewards.shape
         chunk = max(1, min(B, PREPASS_GRAPHS // T))
+        L = self.rnn_step
+        ph = _Phases(self.device)
+        ph.mark()
         info, extra = {}, {}
+        self._flat_reduce = True  # one all-reduce of the whole gradient buffer per minibatch
         for _ in range(self.epoch_ppo):
             # Vl scan over the whole episode + final Vl (informarl.py:310-322)
             Vl = self._vl_all(rollout, chunk)
             Ql, A, extra = self._targets(rollout, Vl, step)
             # minibatches (informarl.py:342-355)
-            L = self.rnn_step
-            assert T % L == 0, "jnp.array(jnp.array_split(...)) in the reference needs rnn_step | T"
-            S_per_env = T // L
-            batches = minibatch_plan(B, T, self.world, self.batch_size, self.np_rng)
-            env_ids = self._env_ids(batches)
-            for bi in batches:
-                envs = next(env_ids)
-                Bm = len(bi)
+            for bi, envs in self._minibatches(B, T):
+                S = len(bi) * (T // L)
                 self.grad_flat.zero_()
-                rg = rollout.graph
-                nodes, edges, recv, send, acts, lp_old, adv, tgt = self._gather(
-                    envs, rg.nodes, rg.edges, rg.receivers, rg.senders, rollout.actions, rollout.log_pis, A, Ql)
-                g = self._graph_batch(nodes, edges, recv, send)
-                v, _, cache = self.Vl.seq_fwd(g, Bm * S_per_env, L)
-                tgt = tgt.view(Bm * S_per_env, L)
-                dv = torch.empty_like(v)
-                vl_loss = torch.empty(1, device=dev)
-                K.l2_loss(v, tgt, dv, vl_loss)
-                self.Vl.seq_bwd(cache, dv)
-                del cache
+                g, acts, lp_old, adv, tgt = self._mb_rows(envs, rollout.graph, rollout.actions, rollout.log_pis, A, Ql)
+                tgt = tgt.view(S, L)
                 acts, lp_old, adv = acts.view(-1, self._action_dim), lp_old.view(-1), adv.view(-1)
-                lp, ent, cache = self.actor.eval_seq_fwd(g, Bm * S_per_env, L, acts, self.entropy_eps)
-                dlp = torch.empty_like(lp)
-                dent = torch.empty_like(ent)
-                stats = torch.empty(4, device=dev)
-                K.ppo_loss(lp, lp_old, adv, ent, self.clip_eps, self.coef_ent, dlp, dent, stats)
-                self.actor.eval_seq_bwd(cache, dlp, dent)
-                del cache
-                self._allreduce_grads()
-                if self.trace is not None:
-                    self.trace.setdefault("mb", []).append(dict(envs=bi.copy(), grad=self.grad_flat.clone()))
-                for name in ("Vl", "policy"):
-                    self.opt[name].step()
+                vl_loss, stats = self._mb_step([
+                    lambda pending: self._vl_pass(g, tgt, S, L, ph, pending),
+                    lambda pending: self._pi_pass(g, acts, lp_old, adv, S, L, ph, pending)], ph)
+                self._trace_mb(bi, vl_loss=vl_loss, stats=stats)
                 info = {"Vl/loss": vl_loss, "Vl/max_target": tgt.max(), "Vl/min_target": tgt.min(),
                         "policy/stats": stats, "policy/log_pi_min": lp_old.min()}
+        self._flat_reduce = False
+        ph.report()
         info.update(extra)
         out = self._finish_info(info)
         for k in ("Vh/grad_Vh_norm", "Vh/grad_Vh_has_nan"):

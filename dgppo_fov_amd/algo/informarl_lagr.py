@@ -17,13 +17,14 @@ import torch
 
 from ..nn import kernels as K
 from ..trainer.rollout import Rollout
-from .dgppo import PREPASS_GRAPHS, DGPPO, minibatch_plan
+from .dgppo import PREPASS_GRAPHS, _Phases
 from .informarl import InforMARL
 from .module.nets import VhGlobalNet
 
 
 class InforMARLLagr(InforMARL):
     VH_NET = VhGlobalNet
+    NETS = ("Vl", "Vh", "policy")
 
     def __init__(self, *args, lagr_init: float = 0.78, lr_lagr: float = 1e-7, **kwargs):
         kwargs.pop("cost_weight", None)  # the reference passes 0 to InforMARL (informarl_lagr.py:58-61)
@@ -54,11 +55,26 @@ class InforMARLLagr(InforMARL):
             out[e0:e1, T].copy_(vf.view(e1 - e0, n, nh))
         return out
 
+    def _vh_pass(self, g, tgt, S, L, ph, pending, h=None):
+        """update_Vh (informarl_lagr.py:246-280): l2 to Qh over S sequences of L graphs from zero carries."""
+        vh, _, cache = self.Vh.seq_fwd(g, S, L)
+        dvh = torch.empty_like(vh)
+        loss = torch.empty(1, device=self.device)
+        K.l2_loss(vh, tgt, dvh, loss)
+        ph.mark("Vh_fwd")
+        with self._wgrad(self.Vh):
+            self.Vh.seq_bwd(cache, dvh)
+        self._start_reduce(self.Vh, pending)
+        ph.mark("Vh_bwd")
+        return loss
+
     def update(self, rollout: Rollout, step: int) -> dict:
         env, dev = self._env, self.device
         B, T = rollout.rewards.shape
         n, nh = self._n_agents, env.n_cost
         chunk = max(1, min(B, PREPASS_GRAPHS // T))
+        ph = _Phases(dev)
+        ph.mark()
         info = {}
         for _ in range(self.epoch_ppo):
             # the Vl and Vh scans are independent: two streams, as DGPPO's prepass
@@ -76,55 +92,19 @@ class InforMARLLagr(InforMARL):
                 self.trace.update(Vl=Vl.clone(), Vh=Vh.clone(), hs=hs.clone(), Ql=Ql.clone(), Qh=Qh.clone(),
                                   A=A.clone(), Ah=Ah.clone(), lagr0=self.ah_lagr.clone(), mb=[])
             L = self.rnn_step
-            assert T % L == 0, "jnp.array(jnp.array_split(...)) in the reference needs rnn_step | T"
-            S_per_env = T // L
-            Vh_T = Vh[:, :T]
             lagr_mean = torch.empty(1, device=dev)
-            batches = minibatch_plan(B, T, self.world, self.batch_size, self.np_rng)
-            env_ids = self._env_ids(batches)
-            for bi in batches:
-                envs = next(env_ids)
+            for bi, envs in self._minibatches(B, T):
                 Bm = len(bi)
+                S = Bm * (T // L)
                 self.grad_flat.zero_()
-                rg = rollout.graph
-                nodes, edges, recv, send, acts, lp_old, adv, tgt, qh, vh_mb, ah_mb = self._gather(
-                    envs, rg.nodes, rg.edges, rg.receivers, rg.senders, rollout.actions, rollout.log_pis, A, Ql, Qh,
-                    Vh_T, Ah)
-                g = self._graph_batch(nodes, edges, recv, send)
-                pending = []
-                # update_Vl (informarl.py:357-385)
-                v, _, cache = self.Vl.seq_fwd(g, Bm * S_per_env, L)
-                tgt = tgt.view(Bm * S_per_env, L)
-                dv = torch.empty_like(v)
-                vl_loss = torch.empty(1, device=dev)
-                K.l2_loss(v, tgt, dv, vl_loss)
-                self.Vl.seq_bwd(cache, dv)
-                del cache
-                self._start_reduce(self.Vl, pending)
-                # update_Vh (informarl_lagr.py:246-280): 16-step chunks from zero carries, l2 to Qh
-                vh, _, cache = self.Vh.seq_fwd(g, Bm * S_per_env, L)
-                dvh = torch.empty_like(vh)
-                vh_loss = torch.empty(1, device=dev)
-                qh = qh.view(-1, nh)
-                K.l2_loss(vh, qh, dvh, vh_loss)
-                self.Vh.seq_bwd(cache, dvh)
-                del cache
-                self._start_reduce(self.Vh, pending)
-                # update_policy (informarl.py:405-457)
+                g, acts, lp_old, adv, tgt, qh, vh_mb, ah_mb = self._mb_rows(
+                    envs, rollout.graph, rollout.actions, rollout.log_pis, A, Ql, Qh, Vh[:, :T], Ah)
+                tgt, qh = tgt.view(S, L), qh.view(-1, nh)
                 acts, lp_old, adv = acts.view(-1, self._action_dim), lp_old.view(-1), adv.view(-1)
-                lp, ent, cache = self.actor.eval_seq_fwd(g, Bm * S_per_env, L, acts, self.entropy_eps)
-                dlp, dent = torch.empty_like(lp), torch.empty_like(ent)
-                stats = torch.empty(4, device=dev)
-                K.ppo_loss(lp, lp_old, adv, ent, self.clip_eps, self.coef_ent, dlp, dent, stats)
-                self.actor.eval_seq_bwd(cache, dlp, dent)
-                del cache
-                self._start_reduce(self.actor, pending)
-                self._finish_reduce(pending)
-                if self.trace is not None:
-                    self.trace["mb"].append(dict(envs=bi.copy(), grad=self.grad_flat.clone(),
-                                                 before={k: o.ps.flat.clone() for k, o in self.opt.items()}))
-                for name in ("Vl", "Vh", "policy"):
-                    self.opt[name].step()
+                vl_loss, vh_loss, stats = self._mb_step([
+                    lambda pending: self._vl_pass(g, tgt, S, L, ph, pending),
+                    lambda pending: self._vh_pass(g, qh, S, L, ph, pending),
+                    lambda pending: self._pi_pass(g, acts, lp_old, adv, S, L, ph, pending)], ph)
                 # update_lagr with the updated policy: whole episodes from zero carries (informarl_lagr.py:283-305)
                 lp_new, _, _ = self.actor.eval_seq_fwd(g, Bm, T, acts, self.entropy_eps)
                 if self.world == 1:
@@ -132,11 +112,11 @@ class InforMARLLagr(InforMARL):
                                   self.lr_lagr)
                 else:
                     self._lagr_step_sharded(lp_new, lp_old, vh_mb, ah_mb, Bm * T, lagr_mean)
-                if self.trace is not None:
-                    self.trace["mb"][-1].update(lp_new=lp_new.clone(), lagr=self.ah_lagr.clone())
+                self._trace_mb(bi, vl_loss=vl_loss, vh_loss=vh_loss, stats=stats, lp_new=lp_new, lagr=self.ah_lagr)
                 info = {"Vl/loss": vl_loss, "Vl/max_target": tgt.max(), "Vl/min_target": tgt.min(),
                         "Vh/loss": vh_loss, "Vh/max_target": qh.max(), "Vh/min_target": qh.min(),
                         "policy/stats": stats, "policy/log_pi_min": lp_old.min(), "policy/lagr_mean": lagr_mean}
+        ph.report()
         out = self._finish_info(info)
         out["Vh/grad_norm"] = out.pop("Vh/grad_Vh_norm")
         out["Vh/has_nan"] = out.pop("Vh/grad_Vh_has_nan")

@@ -215,15 +215,18 @@ class ActorNet(_Net):
         self.gnn.bwd(gc, dz, g, top_masked=fused)
 
 
-class VlNet(_Net):
-    def __init__(self, node_dim: int, n_agents: int, device, seed: int = 1, gnn_layers: int = 2, edge_dim: int = 4,
-                 rnn: str = "gru", rnn_layers: int = 1):
-        self.n = n_agents
+class _ValueNet(_Net):
+    """The shell the value nets share: GNN -> MLP head (HEAD_IN wide input) -> RNN -> Dense(64, n_out)."""
+    HEAD_IN = 64
+
+    def __init__(self, node_dim: int, n_agents: int, n_out: int, device, seed: int = 2, gnn_layers: int = 1,
+                 edge_dim: int = 4, rnn: str = "gru", rnn_layers: int = 1):
+        self.n, self.n_out = n_agents, n_out
         ps = self.ps = ParamSpace()
         self.gnn = GNN(ps, "gnn", node_dim, gnn_layers, edge_dim=edge_dim)
-        self.head = MLPHead(ps, "head")
+        self.head = MLPHead(ps, "head", d_in=self.HEAD_IN)
         self.gru = RNNStack(ps, "gru", rnn, rnn_layers)  # RNN(GRUCell | LSTMCell, layers) or none
-        self.out = Dense(ps, "out", 64, 1)
+        self.out = Dense(ps, "out", 64, n_out)
         self.modules = [self.gnn, self.head, self.gru, self.out]
         ps.build(device)
         self.init_host(seed)
@@ -235,6 +238,11 @@ class VlNet(_Net):
     def load_flax(self, d):
         self.gnn.load_flax(d["gnn"]), self.head.load_flax(d["head"]), self.gru.load_flax(d["gru"])
         self.out.load_flax(d["out"])
+
+
+class VlNet(_ValueNet):
+    def __init__(self, node_dim: int, n_agents: int, device, seed: int = 1, gnn_layers: int = 2, **kwargs):
+        super().__init__(node_dim, n_agents, 1, device, seed, gnn_layers, **kwargs)
 
     def graph_means(self, g: GraphBatch, out=None):
         """The GNN part of the value: the agent mean of the last GNN layer's agent rows, (G, 64) (graphs are
@@ -281,34 +289,14 @@ class VlNet(_Net):
         self.gnn.bwd(gc, dz, g, top_masked=FUSE_LN)
 
 
-class VhNet(_Net):
-    def __init__(self, node_dim: int, n_agents: int, n_cost: int, device, seed: int = 2, gnn_layers: int = 1,
-                 edge_dim: int = 4, rnn: str = "gru", rnn_layers: int = 1):
-        self.n, self.n_cost = n_agents, n_cost
-        ps = self.ps = ParamSpace()
-        self.gnn = GNN(ps, "gnn", node_dim, gnn_layers, edge_dim=edge_dim)
-        self.head = MLPHead(ps, "head")
-        self.gru = RNNStack(ps, "gru", rnn, rnn_layers)  # RNN(GRUCell | LSTMCell, layers) or none
-        self.out = Dense(ps, "out", 64, n_cost)
-        self.modules = [self.gnn, self.head, self.gru, self.out]
-        ps.build(device)
-        self.init_host(seed)
-        self.device = torch.device(device)
-
-    def flax(self):
-        return {"gnn": self.gnn.flax(), "head": self.head.flax(), "gru": self.gru.flax(), "out": self.out.flax()}
-
-    def load_flax(self, d):
-        self.gnn.load_flax(d["gnn"]), self.head.load_flax(d["head"]), self.gru.load_flax(d["gru"])
-        self.out.load_flax(d["out"])
-
+class VhNet(_ValueNet):
     def fwd(self, g: GraphBatch, h: torch.Tensor, keep_cache=True):
         """get_Vh (dgppo.py:128-134) on G graphs with the actor's carries h (G*n, W): (G*n, n_cost).  Forward only
         (keep_cache False): GNN, head, GRU step and output Dense in one kernel where it applies (the prepass)."""
         rows = g.G * self.n
         self.last_tail = False  # True when the fused kernel's value-head tail produced the output (tests)
         if VH_TAIL and not keep_cache and self.gru.simple and len(self.gnn.layers) == 1 and h.shape[1] == 64:
-            out = torch.empty((rows, self.n_cost), device=h.device)
+            out = torch.empty((rows, self.n_out), device=h.device)
             hd, cell = self.head, self.gru.cells[0]
             v = self.ps.view
             tail_w = [hd.d0.W(), hd.d0.b(), v(hd.ln0.name + ".scale"), v(hd.ln0.name + ".bias"), hd.d1.W(), hd.d1.b(),
@@ -334,32 +322,14 @@ class VhNet(_Net):
         self.gnn.bwd(gc, dz, g, top_masked=fused)
 
 
-class VhGlobalNet(_Net):
+class VhGlobalNet(_ValueNet):
     """InforMARL-Lagr's cost critic: ValueNet(n_out=n_cost, decompose=True, use_global_info=True)
     (DecRStateFn, value.py:47-79; informarl_lagr.py:68-79): GNN(agent rows) -> [x | mean over agents of x]
     (n, 128) -> MLP(64, 64) -> GRUCell with its OWN carries (scan_Vh, informarl_lagr.py:152-163) ->
     Dense(n_cost).  The concat never materialises: head Dense_0 = x W[:64] + b + broadcast(mean(x) W[64:])
     (one GEMM of the agent-mean rows, added per graph through the GEMM addend's row grouping)."""
 
-    def __init__(self, node_dim: int, n_agents: int, n_cost: int, device, seed: int = 2, gnn_layers: int = 1,
-                 edge_dim: int = 4, rnn: str = "gru", rnn_layers: int = 1):
-        self.n, self.n_cost = n_agents, n_cost
-        ps = self.ps = ParamSpace()
-        self.gnn = GNN(ps, "gnn", node_dim, gnn_layers, edge_dim=edge_dim)
-        self.head = MLPHead(ps, "head", d_in=128)
-        self.gru = RNNStack(ps, "gru", rnn, rnn_layers)  # RNN(GRUCell | LSTMCell, layers) or none
-        self.out = Dense(ps, "out", 64, n_cost)
-        self.modules = [self.gnn, self.head, self.gru, self.out]
-        ps.build(device)
-        self.init_host(seed)
-        self.device = torch.device(device)
-
-    def flax(self):
-        return {"gnn": self.gnn.flax(), "head": self.head.flax(), "gru": self.gru.flax(), "out": self.out.flax()}
-
-    def load_flax(self, d):
-        self.gnn.load_flax(d["gnn"]), self.head.load_flax(d["head"]), self.gru.load_flax(d["gru"])
-        self.out.load_flax(d["out"])
+    HEAD_IN = 128
 
     def seq_fwd(self, g: GraphBatch, S: int, L: int, h0=None, keep_cache=True):
         """scan_Vh over S sequences of L graphs (zero carries unless h0 (S*n, 64)): values (S*L*n, n_cost) rows

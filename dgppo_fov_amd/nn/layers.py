@@ -862,13 +862,18 @@ class GraphBatch:
     KD0 = 8  # attn.hip kD0
 
     @staticmethod
-    def from_graph(graph, env, flatten_dims=None):
+    def of(env, nodes, edges, receivers, senders):
+        """The graphs of `env` held in four fields with any leading batch dims -> GraphBatch over all of them
+        (row-major; at most one copy per field: a reshape copies only what the constructor would)."""
+        G = nodes.shape[:-2].numel()
+        return GraphBatch(nodes.reshape(G, *nodes.shape[-2:]), edges.reshape(G, *edges.shape[-2:]),
+                          receivers.reshape(G, -1), senders.reshape(G, -1), env.num_agents,
+                          env.agent_candidates(nodes.device), raw_cols=env.nonagent_feature_cols)
+
+    @staticmethod
+    def from_graph(graph, env):
         """GraphsTuple with any leading batch dims -> GraphBatch over all graphs (row-major)."""
-        nd = graph.nodes.dim() - 2
-        G = int(np.prod(graph.nodes.shape[:nd]))
-        return GraphBatch(graph.nodes.reshape(G, *graph.nodes.shape[nd:]), graph.edges.reshape(G, *graph.edges.shape[nd:]),
-                          graph.receivers.reshape(G, -1), graph.senders.reshape(G, -1), env.num_agents,
-                          env.agent_candidates(graph.nodes.device), raw_cols=getattr(env, "nonagent_feature_cols", None))
+        return GraphBatch.of(env, graph.nodes, graph.edges, graph.receivers, graph.senders)
 
     def __init__(self, nodes, edges, receivers, senders, n_agents: int, cand: torch.Tensor, raw_cols=None):
         self.nodes = nodes.contiguous()

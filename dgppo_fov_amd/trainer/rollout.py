@@ -107,9 +107,8 @@ class RolloutEngine:
         return self.env._assemble(b.nodes[t], b.edges[t], b.states[t], b.receivers[t], b.senders[t], self.obstacles)
 
     def _batch(self, t: int, sl=slice(None)) -> GraphBatch:
-        env, b = self.env, self.buf
-        return GraphBatch(b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl], env.num_agents,
-                          env.agent_candidates(self.device), raw_cols=env.nonagent_feature_cols)
+        b = self.buf
+        return GraphBatch.of(self.env, b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl])
 
     def _act_slice(self, t: int, sl: slice, k: int):
         n, A, w = self.env.num_agents, self.env.action_dim, sl.stop - sl.start

@@ -58,3 +58,48 @@ def test_omni_graph_batch_views():
     assert torch.equal(gb.edges_x, torch.from_numpy(edges[..., 4:].copy()))
     with pytest.raises(NotImplementedError):
         GraphBatch(*args).sender_raw
+
+
+@pytest.mark.parametrize("eid", ["LidarSpread", "LidarOmniTarget"])  # 4-wide and 10-wide edges
+def test_graph_batch_of_matches_constructor(eid):
+    """GraphBatch.of flattens any leading batch dims of the four fields and takes the agent count, candidate table
+    and raw_cols from the env: the same batch as the constructor calls it replaces, for an env-major (B, T) rollout
+    (DGPPO._graph_batch), env slices of the (B, T) view of a time-major buffer (DGPPO._graphs) and the last step of
+    a (B, T + 1) buffer (DGPPO._last_graph)."""
+    from dgppo_fov_amd.env import make_env
+
+    B, T, n = 2, 3, 2
+    env = make_env(eid, n, num_obs=2, device="cpu")
+    N, E = env.n_nodes, env.n_edges
+    assert env.edge_dim == (10 if eid == "LidarOmniTarget" else 4)
+    rng = np.random.default_rng(3)
+
+    def fields(*lead):
+        return (torch.from_numpy(rng.standard_normal(lead + (N, env.node_dim)).astype(np.float32)),
+                torch.from_numpy(rng.standard_normal(lead + (E, env.edge_dim)).astype(np.float32)),
+                torch.from_numpy(rng.integers(0, N, lead + (E,)).astype(np.int32)),
+                torch.from_numpy(rng.integers(0, N, lead + (E,)).astype(np.int32)))
+
+    def ctor(nodes, edges, recv, send):  # the call every site wrote out
+        return GraphBatch(nodes, edges, recv, send, n, env.agent_candidates(torch.device("cpu")),
+                          raw_cols=env.nonagent_feature_cols)
+
+    def same(a, b, G):
+        for k in ("nodes", "edges", "receivers", "senders"):
+            x, y = getattr(a, k), getattr(b, k)
+            assert x.is_contiguous() and x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), k
+        assert (a.G, a.N, a.E, a.C, a.n) == (b.G, b.N, b.E, b.C, b.n) == (G, N, E, env.agent_candidates().shape[1], n)
+        assert a.cand is b.cand and a.raw_cols == b.raw_cols == env.nonagent_feature_cols
+
+    # (B, T, ...) contiguous: the gathered minibatch rows
+    f = fields(B, T)
+    same(GraphBatch.of(env, *f), ctor(*(x.view(B * T, *x.shape[2:]) for x in f)), B * T)
+    # a (T, B) buffer viewed as (B, T), sliced by env: the prepass's env chunks of the engine's rollout
+    f = [x.transpose(0, 1) for x in fields(T, B)]
+    for sl in (slice(0, 1), slice(1, 2), slice(0, 2)):
+        Be = sl.stop - sl.start
+        old = ctor(*(x[sl].contiguous().view(Be * T, *x.shape[2:]) for x in f))
+        same(GraphBatch.of(env, *(x[sl] for x in f)), old, Be * T)
+    # [:, -1] of a (B, T + 1, ...) buffer: the final value's graphs
+    f = fields(B, T + 1)
+    same(GraphBatch.of(env, *(x[:, -1] for x in f)), ctor(*(x[:, -1] for x in f)), B)
