@@ -139,6 +139,39 @@ class EnvGraphIO(ctypes.Structure):  # dgppo_env_graph_io
     ]
 
 
+class LidarScanIO(ctypes.Structure):  # dgppo_lidar_scan_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("obstacles", c_f32p), ("obstacles_stride", ctypes.c_int64),
+        ("ray_dirs", c_f32p),
+        ("alpha", c_f32p), ("alpha_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32),
+    ]
+
+
+class LidarHitsIO(ctypes.Structure):  # dgppo_lidar_hits_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("alpha", c_f32p), ("alpha_stride", ctypes.c_int64),
+        ("ray_dirs", c_f32p),
+        ("hits", c_f32p), ("hits_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32),
+    ]
+
+
+class EnvGraphHitsIO(ctypes.Structure):  # dgppo_env_graph_hits_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("goal", c_f32p), ("goal_stride", ctypes.c_int64),
+        ("hits", c_f32p), ("hits_stride", ctypes.c_int64),
+        ("nodes", c_f32p), ("nodes_stride", ctypes.c_int64),
+        ("edges", c_f32p), ("edges_stride", ctypes.c_int64),
+        ("out_states", c_f32p), ("out_states_stride", ctypes.c_int64),
+        ("receivers", c_f32p), ("senders", c_f32p), ("edge_index_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32),
+    ]
+
+
 RENDER_FOV = 1  # include/dgppo_hip.h DGPPO_RENDER_FOV
 
 
@@ -370,6 +403,10 @@ SIGNATURES = {
                                               ctypes.POINTER(EnvRolloutPlan)]),
     "dgppo_env_set_rollout_wpg": (ctypes.c_int, [ctypes.c_int]),
     "dgppo_env_get_graph": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphIO), ctypes.c_void_p]),
+    "dgppo_lidar_scan": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarScanIO), ctypes.c_void_p]),
+    "dgppo_lidar_hits": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarHitsIO), ctypes.c_void_p]),
+    "dgppo_env_get_graph_hits": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphHitsIO),
+                                                ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),

@@ -2999,6 +2999,121 @@ __global__ __launch_bounds__(BLOCK) void env_graph_kernel(dgppo_env_cfg cfg, dgp
   graph_of_staged_rows<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
 }
 
+// ---- sensor in the loop: scan | hits | graph from hits ------------------------------------------
+// get_graph(state, lidar_data) of the reference (lidar_env/base.py:227-271) cut at the seam between the scan and
+// the graph, so the caller can put a sensor model between them.  Plain kernels on the literal arithmetic (no
+// culling): these are not on the benchmarked path.
+
+// A Carve with only the regions the one-agent helpers below touch, for stage_edge_vectors / agent_is_inside
+__device__ __forceinline__ Carve scan_carve() {
+  Carve cv(0, 0, 0, 0, 0, false);
+  cv.obst = 0;                               // (kMaxObs, 16)
+  cv.evec = kMaxObs * DGPPO_OBST_FIELDS;     // (kMaxObs, 8)
+  cv.nxt = cv.evec + kMaxObs * 8;            // the agent's (x, y)
+  cv.isin = cv.nxt + 2;
+  return cv;
+}
+constexpr int kScanLds = kMaxObs * DGPPO_OBST_FIELDS + kMaxObs * 8 + 4;
+
+// dgppo_lidar_scan: one wave per (env, agent), lanes over rays.  alpha[r] = the value lidar_scan ranks: min_nan over
+// obstacles of rect_raytrace, times (1 - is_in) -- the R > 32 branch of lidar_scan, ray by ray.
+__global__ __launch_bounds__(64) void lidar_alpha_kernel(dgppo_env_cfg cfg, dgppo_lidar_scan_io io) {
+  __shared__ __attribute__((aligned(16))) float lds[kScanLds];
+  const int n = cfg.n_agents, O = cfg.n_obs, R = cfg.n_rays, sd = cfg.state_dim;
+  const int lane = threadIdx.x;
+  const int64_t env = blockIdx.x / n;
+  const int i = blockIdx.x - (int)env * n;
+  const Carve cv = scan_carve();
+  const float* ob = io.obstacles + env * io.obstacles_stride;
+  for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) lds[cv.obst + idx] = ob[idx];
+  if (lane < 2) lds[cv.nxt + lane] = io.agent[env * io.agent_stride + i * sd + lane];
+  __syncthreads();
+  stage_edge_vectors(O, lds, cv, lane, 64);
+  if (lane == 0) agent_is_inside(O, lds, cv, 2, 0);
+  __syncthreads();
+  const float* obst = lds + cv.obst;
+  const float* evec = lds + cv.evec;
+  const float sx = lds[cv.nxt], sy = lds[cv.nxt + 1];
+  float* out = io.alpha + env * io.alpha_stride + (int64_t)i * R;
+#pragma unroll 1
+  for (int r = lane; r < R; r += 64) {
+    const float ex = sx + io.ray_dirs[2 * r + 0];
+    const float ey = sy + io.ray_dirs[2 * r + 1];
+    const float ax = sx - ex, ay = sy - ey;
+    float a = 0.0f;
+#pragma unroll 1
+    for (int o = 0; o < O; ++o) {
+      const float ao = rect_raytrace(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
+      a = o == 0 ? ao : min_nan(a, ao);
+    }
+    out[r] = a * (1.0f - lds[cv.isin]);
+  }
+}
+
+// dgppo_lidar_hits: one wave per (env, agent).  The stable NaN-last rank of the caller's alphas by counting smaller
+// sort_keys (lidar_scan's last loop), the hit point by lidar_scan's expression.
+__global__ __launch_bounds__(64) void lidar_hits_kernel(dgppo_env_cfg cfg, dgppo_lidar_hits_io io) {
+  __shared__ uint64_t keys[kMaxRays];
+  const int n = cfg.n_agents, R = cfg.n_rays, k = cfg.top_k, sd = cfg.state_dim;
+  const int lane = threadIdx.x;
+  const int64_t env = blockIdx.x / n;
+  const int i = blockIdx.x - (int)env * n;
+  const float* al = io.alpha + env * io.alpha_stride + (int64_t)i * R;
+  const float sx = io.agent[env * io.agent_stride + i * sd + 0];
+  const float sy = io.agent[env * io.agent_stride + i * sd + 1];
+  for (int r = lane; r < R; r += 64) keys[r] = sort_key(al[r], r);
+  __syncthreads();
+  float* hits = io.hits + env * io.hits_stride + (int64_t)i * k * 2;
+#pragma unroll 1
+  for (int r = lane; r < R; r += 64) {
+    const uint64_t key = keys[r];
+    int rank = 0;
+    for (int j = 0; j < R; ++j) rank += keys[j] < key ? 1 : 0;
+    if (rank < k) {
+      const float a = al[r];
+      const float ex = sx + io.ray_dirs[2 * r + 0];
+      const float ey = sy + io.ray_dirs[2 * r + 1];
+      hits[rank * 2 + 0] = sx + (ex - sx) * a;
+      hits[rank * 2 + 1] = sy + (ey - sy) * a;
+    }
+  }
+}
+
+// dgppo_env_get_graph_hits: env_graph_kernel with the hit rows loaded from the caller's (n, k, 2) tensor into
+// lds + cv.hits instead of ray-cast; then the same write_graph / write_graph_omni.  No obstacles are read.
+template <int ENGINE, int GOAL, int SD, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void env_graph_hits_kernel(dgppo_env_cfg cfg, dgppo_env_graph_hits_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Dims<0, -1, 0, 0> d(cfg);
+  const int n = d.n, k = d.k;
+  const Carve cv(n, SD, d.O, cfg.n_rays, k, true);
+  const int tid = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  float* nxt = lds + cv.nxt;
+  float* goal = lds + cv.cur + n * SD;
+  const float* ag = io.agent + env * io.agent_stride;
+  const float* gl = io.goal + env * io.goal_stride;
+  const float* ht = io.hits + env * io.hits_stride;
+  for (int idx = tid; idx < n * SD; idx += BLOCK) {
+    nxt[idx] = ag[idx];
+    goal[idx] = gl[idx];
+  }
+  for (int idx = tid; idx < n * k * 2; idx += BLOCK) lds[cv.hits + idx] = ht[idx];
+  __syncthreads();
+  GraphOut out;
+  out.nodes = io.nodes + env * io.nodes_stride;
+  out.edges = io.edges + env * io.edges_stride;
+  out.states = io.out_states + env * io.out_states_stride;
+  out.recv = io.receivers + env * io.edge_index_stride;
+  out.send = io.senders + env * io.edge_index_stride;
+  if constexpr (ENGINE == DGPPO_ENGINE_OMNI) {
+    write_graph_omni(cfg, n, k, true, nxt, goal, lds + cv.hits, out, tid, BLOCK);
+  } else {
+    const bool vec4 = ((io.edges_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(io.edges) & 15) == 0);
+    write_graph<ENGINE, GOAL, SD>(cfg, d, nxt, goal, lds + cv.hits, out, vec4, tid, BLOCK);
+  }
+}
+
 // ---- reference env variants ------------------------------------------------------------------
 // lidar_line.py, mpe_line.py, mpe_formation.py, mpe_corridor.py, mpe_connect_spread.py: the SPREAD
 // double-integrator envs with `n_goals` goal node rows (2 landmarks / 1 landmark / one per agent),
@@ -3477,6 +3592,33 @@ __global__ __launch_bounds__(kT) void graph_kernel(dgppo_env_cfg cfg, dgppo_env_
   }
   __syncthreads();
   graph_of_staged_rows_var<ENGINE>(cfg, io, d, cv, lds, env);
+}
+
+// LidarLine's graph from caller-given hit rows (dgppo_env_get_graph_hits): graph_kernel with the (n, k, 2) hits loaded
+// into lds + cv.hits instead of ray-cast, then the same write_graph_var.
+__global__ __launch_bounds__(kT) void graph_hits_kernel(dgppo_env_cfg cfg, dgppo_env_graph_hits_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int SD = 4;
+  const Dims<0, -1, 0, 0> d(cfg);
+  const int n = d.n, ng = cfg.n_goals;
+  const Carve cv(n, SD, d.O, d.R, d.k, true);
+  float* grow = lds + cv.cur + n * SD;  // goal node rows
+  const int tid = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  const float* ag = io.agent + env * io.agent_stride;
+  const float* gl = io.goal + env * io.goal_stride;
+  const float* ht = io.hits + env * io.hits_stride;
+  for (int idx = tid; idx < n * SD; idx += kT) lds[cv.nxt + idx] = ag[idx];
+  for (int idx = tid; idx < ng * SD; idx += kT) grow[idx] = gl[idx];
+  for (int idx = tid; idx < n * d.k * 2; idx += kT) lds[cv.hits + idx] = ht[idx];
+  __syncthreads();
+  GraphOut out;
+  out.nodes = io.nodes + env * io.nodes_stride;
+  out.edges = io.edges + env * io.edges_stride;
+  out.states = io.out_states + env * io.out_states_stride;
+  out.recv = io.receivers + env * io.edge_index_stride;
+  out.send = io.senders + env * io.edge_index_stride;
+  write_graph_var(cfg, false, true, lds + cv.nxt, grow, lds + cv.hits, out, tid, kT);
 }
 
 // the one launch of the step, reset and graph kernels: LDS size, the 64 KB check, the MPE or the LIDAR instance
@@ -4192,6 +4334,53 @@ extern "C" int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_gra
   const size_t shmem = (size_t)cv.total * sizeof(float);
   if (shmem > 64 * 1024) return DGPPO_EINVAL;
   dispatch_graph(*cfg, *io, shmem, s);
+  return (int)hipGetLastError();
+}
+
+// the sensor entry points' common gate: a valid Lidar-engine cfg with obstacles to sense (0), else DGPPO_EINVAL
+static int validate_sensor(const dgppo_env_cfg* cfg) {
+  if (validate(cfg) || vmas::is_vmas(cfg)) return DGPPO_EINVAL;
+  if (cfg->engine == DGPPO_ENGINE_MPE || cfg->n_obs < 1) return DGPPO_EINVAL;
+  return 0;
+}
+
+extern "C" int dgppo_lidar_scan(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream) {
+  if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->obstacles || !io->ray_dirs || !io->alpha) return DGPPO_EINVAL;
+  const int64_t waves = (int64_t)io->n_env * cfg->n_agents;  // one per (env, agent)
+  if (waves > INT32_MAX) return DGPPO_EINVAL;
+  hipLaunchKernelGGL(lidar_alpha_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, *cfg, *io);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dgppo_lidar_hits(const dgppo_env_cfg* cfg, const dgppo_lidar_hits_io* io, void* stream) {
+  if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->alpha || !io->ray_dirs || !io->hits) return DGPPO_EINVAL;
+  const int64_t waves = (int64_t)io->n_env * cfg->n_agents;
+  if (waves > INT32_MAX) return DGPPO_EINVAL;
+  hipLaunchKernelGGL(lidar_hits_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, *cfg, *io);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dgppo_env_get_graph_hits(const dgppo_env_cfg* cfg, const dgppo_env_graph_hits_io* io, void* stream) {
+  if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->goal || !io->hits || !io->nodes || !io->edges || !io->out_states || !io->receivers ||
+      !io->senders)
+    return DGPPO_EINVAL;
+  const hipStream_t s = (hipStream_t)stream;
+  if (cfg->variant != DGPPO_VARIANT_NONE) return var::launch(var::graph_hits_kernel, var::graph_hits_kernel, *cfg, *io, s);
+  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k, true);
+  const size_t shmem = (size_t)cv.total * sizeof(float);
+  if (shmem > 64 * 1024) return DGPPO_EINVAL;
+  visit_engine_goal(*cfg, [&](auto e) {
+    using E = decltype(e);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
+      hipLaunchKernelGGL((env_graph_hits_kernel<E::ENGINE, E::GOAL, E::SD, 128>), dim3((unsigned)io->n_env), dim3(128),
+                         shmem, s, *cfg, *io);
+  });
   return (int)hipGetLastError();
 }
 

@@ -370,11 +370,11 @@ class MultiAgentEnv(ABC):
     def _third_name(self) -> str:
         return "obstacle" if self._obstacle_fields() > 0 else "obs"
 
-    def state_rows(self, state, what: str = "get_graph: state"):
+    def state_rows(self, state, what: str = "get_graph: state", third_optional: bool = False):
         """Check an env state tuple's shapes and return (agent (B, n, sd), goal (B, n_goal_rows, sd), third, B), third
         = the (B, O, F) obstacle tensor the graph kernel reads (None when n_obs == 0): the Lidar records (F = 16; a
         Rectangle or its packed tensor) or the MPE obstacle states (F = 4).  A mismatch raises a ValueError naming the
-        field as `what`.<field>."""
+        field as `what`.<field>.  third_optional: a missing / None third passes as None (sensor-only states)."""
         if not isinstance(state, tuple) or len(state) < 2:
             raise ValueError(f"{what} must be the env's (agent, goal, {self._third_name()}) state tuple")
         agent, goal = state[0], state[1]
@@ -390,20 +390,29 @@ class MultiAgentEnv(ABC):
         if self.n_obs > 0:
             third = state[2] if len(state) > 2 else None
             third = getattr(third, "packed", third)
+            if third is None and third_optional:
+                return agent, goal, None, B
             fields = self._obstacle_fields() or sd
             if not isinstance(third, torch.Tensor) or tuple(third.shape) != (B, self.n_obs, fields):
                 got = tuple(third.shape) if isinstance(third, torch.Tensor) else type(third).__name__
                 raise ValueError(f"{what}.{self._third_name()} must be ({B}, {self.n_obs}, {fields}), got {got}")
         return agent, goal, third, B
 
-    def get_graph(self, state, out: Optional[GraphsTuple] = None) -> GraphsTuple:
+    def get_graph(self, state, out: Optional[GraphsTuple] = None, *, lidar_data: Optional[torch.Tensor] = None
+                  ) -> GraphsTuple:
         """Batched `vmap(env.get_graph)` with get_lidar_data (dgppo/env/base.py:137, lidar_env/base.py:227-271,
         mpe/base.py:211-241): the graph of the caller's own state, one HIP launch (torch.ops.dgppo.env_get_graph).
 
         `state` is this env's state tuple with one leading env axis: (agent (B, n, sd), goal (B, n_goal_rows, sd),
         obstacle), the obstacle a Rectangle / packed (B, O, 16) tensor (Lidar), the (B, O, 4) obstacle states (MPE),
         or None when n_obs == 0.  `graph.env_states` of any graph of this env is a valid argument.  Nothing is
-        clipped.  The returned graph carries the obstacles, so `env.step(env.get_graph(s), a)` works."""
+        clipped.  The returned graph carries the obstacles, so `env.step(env.get_graph(s), a)` works.
+
+        lidar_data (B, n, top_k, 2), Lidar envs only: the graph is built from these hit points instead of a ray cast
+        (the reference's get_graph(state, lidar_data); torch.ops.dgppo.env_get_graph_hits).  The state's obstacle may
+        then be None (a sensor-only graph: `env.step` on it raises) or given (carried on the graph for `step`)."""
+        if lidar_data is not None:
+            return self._get_graph_hits(state, out, lidar_data)
         agent, goal, third, B = self.state_rows(state)
         dev = agent.device if out is None else out.nodes.device
         _lib.require_gpu(dev, "env.get_graph")
@@ -437,6 +446,88 @@ class MultiAgentEnv(ABC):
         goal = agent_states.new_zeros((agent_states.shape[0], ng, self.state_dim))
         g = self.get_graph((agent_states, goal, obstacles))
         return g.states[:, n + ng:n + ng + n * k, :2].reshape(-1, n, k, 2)
+
+    # ---- sensor in the loop: scan | hits | graph from hits ------------------------------------------
+    def _require_lidar(self, what: str) -> None:
+        if self.ENGINE in self._VMAS_ENGINES:
+            raise NotImplementedError(f"{what}: the VMAS envs have no LiDAR sensor model")
+        if self._obstacle_fields() == 0 or self.n_obs == 0:
+            raise ValueError(f"{what}: this env has no LiDAR")
+
+    @staticmethod
+    def _sensor_arg(what: str, name: str, t, shape, dev=None) -> torch.Tensor:
+        """A float32 tensor of exactly `shape` (on `dev` when given) with contiguous rows, else a ValueError naming it."""
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
+            got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {got}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{what}: {name} is on {t.device}, expected {dev}")
+        tail = 1  # the per-env stride is free (views of a rollout buffer); the dims behind it must be contiguous
+        for d in range(t.dim() - 1, 0, -1):
+            if t.stride(d) != tail:
+                return t.contiguous()
+            tail *= t.shape[d]
+        return t
+
+    def _sensor_agents(self, what: str, agent_states) -> torch.Tensor:
+        if not isinstance(agent_states, torch.Tensor) or agent_states.dim() != 3:
+            got = tuple(agent_states.shape) if isinstance(agent_states, torch.Tensor) else type(agent_states).__name__
+            raise ValueError(f"{what}: agent_states must be (B, {self._num_agents}, {self.state_dim}), got {got}")
+        B = int(agent_states.shape[0])
+        return self._sensor_arg(what, "agent_states", agent_states, (B, self._num_agents, self.state_dim))
+
+    def lidar_scan(self, agent_states: torch.Tensor, obstacles) -> torch.Tensor:
+        """The raw scan (torch.ops.dgppo.lidar_scan): alpha (B, n, R) of the agents at `agent_states` (B, n, sd)
+        among `obstacles` (a Rectangle or its packed (B, O, 16) tensor): per beam the fraction of the sensing range
+        to the nearest obstacle edge, 1e6 where nothing is hit, 0 for an agent inside an obstacle -- the values
+        get_lidar_data ranks (env/utils.py:115-130).  `lidar_hits(agent_states, alpha)` turns them (or an edited
+        copy: utils/sensor.py) into hit points."""
+        what = "lidar_scan"
+        self._require_lidar(what)
+        agent = self._sensor_agents(what, agent_states)
+        B = int(agent.shape[0])
+        ob = self._sensor_arg(what, "obstacles", getattr(obstacles, "packed", obstacles),
+                              (B, self.n_obs, self._obstacle_fields()), agent.device)
+        _lib.require_gpu(agent.device, "env.lidar_scan")
+        alpha = torch.empty((B, self._num_agents, int(self._params["n_rays"])), dtype=torch.float32,
+                            device=agent.device)
+        torch.ops.dgppo.lidar_scan(self._cfg_handle, agent, ob, self._ray_table(agent.device), alpha)
+        return alpha
+
+    def lidar_hits(self, agent_states: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
+        """Scan to hit points (torch.ops.dgppo.lidar_hits): (B, n, top_k, 2), the top_k smallest of `alpha` (B, n, R)
+        per agent in the reference's order (stable argsort, NaN last), each the point start + ray * alpha.
+        `lidar_hits(a, lidar_scan(a, ob))` is `get_lidar_data(a, ob)` bit for bit."""
+        what = "lidar_hits"
+        self._require_lidar(what)
+        agent = self._sensor_agents(what, agent_states)
+        B, n = int(agent.shape[0]), self._num_agents
+        alpha = self._sensor_arg(what, "alpha", alpha, (B, n, int(self._params["n_rays"])), agent.device)
+        _lib.require_gpu(agent.device, "env.lidar_hits")
+        hits = torch.empty((B, n, int(self._params["top_k_rays"]), 2), dtype=torch.float32, device=agent.device)
+        torch.ops.dgppo.lidar_hits(self._cfg_handle, agent, alpha, self._ray_table(agent.device), hits)
+        return hits
+
+    def _get_graph_hits(self, state, out: Optional[GraphsTuple], lidar_data) -> GraphsTuple:
+        what = "get_graph"
+        self._require_lidar(what + ": lidar_data")
+        agent, goal, third, B = self.state_rows(state, third_optional=True)
+        dev = agent.device if out is None else out.nodes.device
+        n, sd = self._num_agents, self.state_dim
+        agent = self._sensor_arg(what, "state.agent", agent, (B, n, sd), dev)
+        goal = self._sensor_arg(what, "state.goal", goal, (B, self.num_goals, sd), dev)
+        hits = self._sensor_arg(what, "lidar_data", lidar_data, (B, n, int(self._params["top_k_rays"]), 2), dev)
+        if third is not None:  # not read here: carried on the graph for step
+            third = self._sensor_arg(what, "state.obstacle", third, (B, self.n_obs, self._obstacle_fields()), dev)
+        _lib.require_gpu(dev, "env.get_graph")
+        g = self.empty_graph((B,), dev) if out is None else out
+        if g.states.dim() != 3 or g.states.shape[0] != B:
+            raise ValueError(f"get_graph: out must hold {B} graphs")
+        torch.ops.dgppo.env_get_graph_hits(self._cfg_handle, agent, goal, hits, g.nodes, g.edges, g.states,
+                                           g.receivers, g.senders)
+        return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
     def get_reward(self, graph: GraphsTuple, action: torch.Tensor) -> torch.Tensor:
         """Reward (B,) of taking `action` in `graph` (lidar_spread.py:35-52, ...): the step kernel evaluates it."""

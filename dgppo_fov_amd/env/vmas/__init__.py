@@ -130,7 +130,7 @@ class VMASEnv(MultiAgentEnv):
         g = super()._assemble(nodes, edges, states, recv, send, obstacles)
         return g._replace(env_states=self._env_states(states, obstacles, nodes))
 
-    def get_graph(self, state, out=None) -> GraphsTuple:
+    def get_graph(self, state, out=None, *, lidar_data=None) -> GraphsTuple:
         raise NotImplementedError("VMAS envs: get_graph of given states is not supported (the env record carries "
                                   "contact-physics state); use reset / step")
 

@@ -12,6 +12,9 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::env_reset_states dgppo_env_reset_states  the sampling half of env_reset (no graph)
   dgppo::env_rollout    dgppo_env_rollout    lax.scan of env.step over T given actions, trainer/utils.py:45-55
   dgppo::env_get_graph  dgppo_env_get_graph  vmap(env.get_graph)  lidar_env/base.py:126-140, 227-271, mpe/base.py:211-241
+  dgppo::lidar_scan     dgppo_lidar_scan     the per-beam alphas of get_lidar, env/utils.py:115-130
+  dgppo::lidar_hits     dgppo_lidar_hits     alphas -> top-k hit points, env/utils.py:66-79
+  dgppo::env_get_graph_hits dgppo_env_get_graph_hits  get_graph(state, lidar_data), lidar_env/base.py:227-271
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
@@ -268,6 +271,74 @@ def env_get_graph(cfg: int, agent: Tensor, goal: Tensor, third: Optional[Tensor]
 
 @env_get_graph.register_fake
 def _env_get_graph_fake(cfg, agent, goal, third, ray_dirs, nodes, edges, states, receivers, senders) -> None:
+    return None
+
+
+# ---- sensor in the loop: scan | hits | graph from hits ---------------------------------------------------
+@torch.library.custom_op("dgppo::lidar_scan", mutates_args=("alpha",))
+def lidar_scan(cfg: int, agent: Tensor, obstacles: Tensor, ray_dirs: Tensor, alpha: Tensor) -> None:
+    """The raw LiDAR scan of B envs: agent (B, n, sd) rows and obstacle records (B, O, 16) -> alpha (B, n, R), per
+    beam the value get_lidar sorts (1e6 = no return, 0 inside an obstacle, NaN propagates).  Per-env strides are
+    free; the trailing dims must be contiguous."""
+    _lib.require_gpu(alpha.device, "dgppo::lidar_scan")
+    io = _lib.LidarScanIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.obstacles, io.obstacles_stride = _p(obstacles), _stride(obstacles, 2)
+    io.ray_dirs = _p(ray_dirs)
+    io.alpha, io.alpha_stride = _p(alpha), _stride(alpha, 2)
+    io.n_env = int(agent.shape[0])
+    _lib.check(_lib.load().dgppo_lidar_scan(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(alpha)),
+               "dgppo_lidar_scan")
+
+
+@lidar_scan.register_fake
+def _lidar_scan_fake(cfg, agent, obstacles, ray_dirs, alpha) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::lidar_hits", mutates_args=("hits",))
+def lidar_hits(cfg: int, agent: Tensor, alpha: Tensor, ray_dirs: Tensor, hits: Tensor) -> None:
+    """Scan to hit points: agent (B, n, sd) rows and the caller's alpha (B, n, R) -> hits (B, n, top_k, 2), the top_k
+    smallest alphas in jnp.argsort's order (stable, NaN last, -0 == +0) as points start + ray * alpha."""
+    _lib.require_gpu(hits.device, "dgppo::lidar_hits")
+    io = _lib.LidarHitsIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.alpha, io.alpha_stride = _p(alpha), _stride(alpha, 2)
+    io.ray_dirs = _p(ray_dirs)
+    io.hits, io.hits_stride = _p(hits), _stride(hits, 3)
+    io.n_env = int(agent.shape[0])
+    _lib.check(_lib.load().dgppo_lidar_hits(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(hits)),
+               "dgppo_lidar_hits")
+
+
+@lidar_hits.register_fake
+def _lidar_hits_fake(cfg, agent, alpha, ray_dirs, hits) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::env_get_graph_hits", mutates_args=("nodes", "edges", "states", "receivers",
+                                                                     "senders"))
+def env_get_graph_hits(cfg: int, agent: Tensor, goal: Tensor, hits: Tensor, nodes: Tensor, edges: Tensor,
+                       states: Tensor, receivers: Tensor, senders: Tensor) -> None:
+    """env_get_graph with the LiDAR hit rows given: agent (B, n, sd), goal (B, n_goal_rows, sd) and hits
+    (B, n, top_k, 2) -> the graph rows (get_graph's lidar_data argument).  No obstacles are read."""
+    _lib.require_gpu(states.device, "dgppo::env_get_graph_hits")
+    io = _lib.EnvGraphHitsIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.goal, io.goal_stride = _p(goal), _stride(goal, 2)
+    io.hits, io.hits_stride = _p(hits), _stride(hits, 3)
+    io.nodes, io.nodes_stride = _p(nodes), _stride(nodes, 2)
+    io.edges, io.edges_stride = _p(edges), _stride(edges, 2)
+    io.out_states, io.out_states_stride = _p(states), _stride(states, 2)
+    io.receivers, io.senders = _p(receivers), _p(senders)
+    io.edge_index_stride = _stride(receivers, 1)
+    io.n_env = int(agent.shape[0])
+    _lib.check(_lib.load().dgppo_env_get_graph_hits(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
+               "dgppo_env_get_graph_hits")
+
+
+@env_get_graph_hits.register_fake
+def _env_get_graph_hits_fake(cfg, agent, goal, hits, nodes, edges, states, receivers, senders) -> None:
     return None
 
 

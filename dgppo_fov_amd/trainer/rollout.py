@@ -229,3 +229,63 @@ class RolloutEngine:
             log_pis = self.log_pis.transpose(0, 1) if self.mode == self.MODE_SAMPLE else None
         return Rollout(view(slice(0, T)), self.actions.transpose(0, 1), rnn, self.rewards.transpose(0, 1),
                        self.costs.transpose(0, 1), self.dones.transpose(0, 1), log_pis, view(slice(1, T + 1)))
+
+
+class SensorRolloutEngine(RolloutEngine):
+    """RolloutEngine with a LiDAR sensor model between the world and the policy.
+
+    Per step t: alpha = env.lidar_scan(agent_t, obstacles); alpha_obs = sensor(alpha, t); the OBSERVED graph is
+    env.get_graph(true state_t, lidar_data=env.lidar_hits(agent_t, alpha_obs)); the actor acts on it; env.step_into
+    advances the TRUE graph (true obstacles, true ray cast) and writes the true reward and cost.  So the truth
+    depends on the observation through the actions only, `run` returns the true Rollout (metrics and videos mean
+    what they meant), and the observed graphs are `engine.observed`, batch shape (B, T).
+
+    sensor: a callable (alpha (B, n, R), t) -> alpha_obs of the same shape, dtype and device (utils/sensor.py has
+    LidarNoise; `lambda a, t: a` reproduces the plain engine bit for bit).  MODE_DET or MODE_SAMPLE with an actor,
+    one lane, a Lidar env with obstacles; no hipGraph capture (a sensor is arbitrary Python)."""
+
+    def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
+                 actor=None, mode: int = RolloutEngine.MODE_DET, sensor=None, init_state=None):
+        if not callable(sensor):
+            raise ValueError("SensorRolloutEngine: sensor must be a callable (alpha, t) -> alpha_obs")
+        if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
+            raise ValueError("SensorRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
+        env._require_lidar("SensorRolloutEngine")
+        super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
+        self.sensor = sensor
+        self.obs_buf = env.empty_graph((self.T, self.B), self.device)  # time-major, like buf
+
+    def _observed_at(self, t: int) -> GraphsTuple:
+        b = self.obs_buf
+        return self.env._assemble(b.nodes[t], b.edges[t], b.states[t], b.receivers[t], b.senders[t], self.obstacles)
+
+    def _batch(self, t: int, sl=slice(None)) -> GraphBatch:  # the actor's input: the observed graph of step t
+        b = self.obs_buf
+        return GraphBatch.of(self.env, b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl])
+
+    def _run(self):
+        env, n = self.env, self.env.num_agents
+        if self.init_state is not None:
+            cur = env.get_graph(self.init_state, out=self.graph_at(0))
+        else:
+            cur = env.reset(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
+                            obstacles_out=self.obstacles)
+        for t in range(self.T):
+            agent = self.buf.states[t][:, :n]
+            goal = self.buf.states[t][:, n:n + env.num_goals]
+            alpha_obs = self.sensor(env.lidar_scan(agent, self.obstacles), t)
+            env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
+                          lidar_data=env.lidar_hits(agent, alpha_obs))
+            self._act(t)
+            cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
+
+    def capture(self):
+        raise NotImplementedError("SensorRolloutEngine: hipGraph capture of the sensor loop is not built")
+
+    @property
+    def observed(self) -> GraphsTuple:
+        """The graphs the actor saw, batch shape (B, T): (B, T, ...) views of the time-major buffer."""
+        b = self.obs_buf
+        tr = lambda x: x.transpose(0, 1)  # noqa: E731
+        return self.env._assemble(tr(b.nodes), tr(b.edges), tr(b.states), tr(b.receivers), tr(b.senders),
+                                  self.obstacles)

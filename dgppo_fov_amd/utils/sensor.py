@@ -1,0 +1,78 @@
+"""Sensor models for the LiDAR envs: what sits between `env.lidar_scan` and `env.lidar_hits`.
+
+The scan is `alpha` (B, n, R): per beam the hit distance as a fraction of the sensing range (the env's
+comm_radius), NO_RETURN = 1e6 where nothing is hit (the reference's env/utils.py:115-130).  A sensor is any callable
+`sensor(alpha, t) -> alpha_obs` of the same shape and device; trainer/rollout.py SensorRolloutEngine runs one in the
+loop, `env.get_graph(state, lidar_data=env.lidar_hits(agent, alpha_obs))` builds a graph from its output.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from .. import _lib
+
+NO_RETURN = 1e6  # the reference's alpha of a beam that hits nothing
+
+
+def ranges_to_alpha(ranges: torch.Tensor, sense_range: float) -> torch.Tensor:
+    """Range readings in metres (any shape; a real sensor's or a recorded scan's) -> alpha for `env.lidar_hits`:
+    ranges / sense_range, with non-finite readings and readings outside [0, sense_range] as NO_RETURN."""
+    if not isinstance(ranges, torch.Tensor) or not ranges.is_floating_point():
+        raise ValueError("ranges_to_alpha: ranges must be a floating-point tensor")
+    if not (math.isfinite(sense_range) and sense_range > 0):
+        raise ValueError(f"ranges_to_alpha: sense_range must be positive and finite, got {sense_range}")
+    r = ranges.to(torch.float32)
+    ok = torch.isfinite(r) & (r >= 0) & (r <= sense_range)
+    return torch.where(ok, r / sense_range, torch.full_like(r, NO_RETURN))
+
+
+class LidarNoise:
+    """Range noise and beam dropout: `LidarNoise(sigma, dropout, seed)(alpha, t)`.
+
+    Beams with a return (alpha <= 1) get additive Gaussian range noise of std `sigma` world units (sigma /
+    sense_range in alpha), floored at 0; then each beam is independently replaced by NO_RETURN with probability
+    `dropout`.  Non-returns and NaN pass through.  The draws come from the project's Philox generator
+    (dgppo_normal) keyed (seed, stream id), the stream ids 2^62 + 2t and 2^62 + 2t + 1: reproducible for a seed,
+    independent across t, and disjoint from the policy's sampling streams ((env_offset << 32) | t, env_offset <
+    2^30; bit 63 is the generator's own domain bit).  A dropout decision is `z < Phi^-1(dropout)` on a standard
+    normal z.  sigma = 0 and dropout = 0 returns the input tensor itself."""
+
+    STREAM_BASE = 1 << 62
+
+    def __init__(self, sigma: float = 0.0, dropout: float = 0.0, seed: int = 0, sense_range: float = 0.5):
+        if not (math.isfinite(sigma) and sigma >= 0):
+            raise ValueError(f"LidarNoise: sigma must be >= 0, got {sigma}")
+        if not 0.0 <= dropout <= 1.0:
+            raise ValueError(f"LidarNoise: dropout must be in [0, 1], got {dropout}")
+        if not (math.isfinite(sense_range) and sense_range > 0):
+            raise ValueError(f"LidarNoise: sense_range must be positive, got {sense_range}")
+        self.sigma, self.dropout, self.seed, self.sense_range = float(sigma), float(dropout), int(seed), float(sense_range)
+        if self.dropout <= 0.0:
+            self._drop_below = -math.inf
+        elif self.dropout >= 1.0:
+            self._drop_below = math.inf
+        else:  # Phi^-1(p) = sqrt(2) erfinv(2p - 1)
+            self._drop_below = math.sqrt(2.0) * float(torch.erfinv(torch.tensor(2.0 * self.dropout - 1.0,
+                                                                                 dtype=torch.float64)))
+
+    def __call__(self, alpha: torch.Tensor, t: int) -> torch.Tensor:
+        if self.sigma == 0.0 and self.dropout == 0.0:
+            return alpha
+        from ..nn import kernels as K
+
+        _lib.require_gpu(alpha.device, "LidarNoise")
+        if alpha.dtype != torch.float32:
+            raise ValueError(f"LidarNoise: alpha must be float32, got {alpha.dtype}")
+        out = alpha
+        z = torch.empty(alpha.shape, dtype=torch.float32, device=alpha.device)
+        if self.sigma > 0.0:
+            K.normal_(z, seed=self.seed, stream_id=self.STREAM_BASE + 2 * int(t))
+            noisy = torch.clamp_min(alpha + z * (self.sigma / self.sense_range), 0.0)
+            out = torch.where(alpha <= 1.0, noisy, alpha)
+        if self.dropout > 0.0:
+            K.normal_(z, seed=self.seed, stream_id=self.STREAM_BASE + 2 * int(t) + 1)
+            drop = (z < self._drop_below) & ~torch.isnan(alpha)
+            out = torch.where(drop, torch.full_like(alpha, NO_RETURN), out)
+        return out

@@ -211,6 +211,59 @@ typedef struct dgppo_env_graph_io {
 
 int dgppo_env_get_graph(const dgppo_env_cfg* cfg, const dgppo_env_graph_io* io, void* stream);
 
+/* Sensor in the loop: the seam between "scan" and "graph" of LidarEnv.get_graph(state, lidar_data)
+ * (dgppo/env/lidar_env/base.py:227-271), so a caller can edit the per-beam ranges (a noisy sensor model, a
+ * recorded scan) or supply the hit points itself.  Three entry points for the Lidar engines with n_obs > 0 (double
+ * integrator, bicycle, omni, LidarLine); each is one launch on `stream`, no host synchronisation, no allocation,
+ * per-env strides in elements.  n_env == 0 returns 0 before any pointer is looked at; a NULL pointer, the MPE and
+ * VMAS engines and n_obs == 0 return DGPPO_EINVAL without a launch.  No ABI number change (new symbols only).
+ *
+ * dgppo_lidar_scan: `agent` (n, sd) rows (columns 0, 1 are read), `obstacles` (O, 16) records, `ray_dirs` (R, 2) ->
+ * `alpha` (n, R): for every beam the value get_lidar sorts (dgppo/env/utils.py:115-130): the min over obstacles of
+ * Rectangle.raytracing (1e6 = no return), times (1 - is_in); NaN propagates.  Every (agent, obstacle, ray) triple is
+ * cast (no culling): the same bits as the culling kernels of dgppo_env_step, by the literal arithmetic. */
+typedef struct dgppo_lidar_scan_io {
+  const float* agent;       int64_t agent_stride;
+  const float* obstacles;   int64_t obstacles_stride;
+  const float* ray_dirs;
+  float* alpha;             int64_t alpha_stride;
+  int32_t n_env;
+} dgppo_lidar_scan_io;
+
+int dgppo_lidar_scan(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream);
+
+/* dgppo_lidar_hits: `agent` (n, sd) rows, the caller's `alpha` (n, R) and `ray_dirs` -> `hits` (n, top_k, 2): the
+ * top_k smallest alphas by jnp.argsort's rule (stable: ties by ray index; NaN last; -0 == +0), each as the point
+ * start + (end - start) * alpha with end = start + ray (dgppo/env/utils.py:66-79; multiply and add rounded
+ * separately).  dgppo_lidar_hits of dgppo_lidar_scan's alpha = the hit rows of dgppo_env_get_graph.  `hits` must not
+ * alias the inputs. */
+typedef struct dgppo_lidar_hits_io {
+  const float* agent;       int64_t agent_stride;
+  const float* alpha;       int64_t alpha_stride;
+  const float* ray_dirs;
+  float* hits;              int64_t hits_stride;
+  int32_t n_env;
+} dgppo_lidar_hits_io;
+
+int dgppo_lidar_hits(const dgppo_env_cfg* cfg, const dgppo_lidar_hits_io* io, void* stream);
+
+/* dgppo_env_get_graph_hits: dgppo_env_get_graph with the LiDAR hit rows `hits` (n, top_k, 2) given by the caller
+ * instead of ray-cast (get_graph's lidar_data argument): same graph writers, so the same graph for the same hits.
+ * `agent`, `goal` and the outputs as in dgppo_env_graph_io; obstacles are neither read nor required.  An env's
+ * outputs may alias that env's own inputs (all rows are staged before any store). */
+typedef struct dgppo_env_graph_hits_io {
+  const float* agent;       int64_t agent_stride;
+  const float* goal;        int64_t goal_stride;
+  const float* hits;        int64_t hits_stride;
+  float* nodes;             int64_t nodes_stride;
+  float* edges;             int64_t edges_stride;
+  float* out_states;        int64_t out_states_stride;
+  int32_t* receivers;       int32_t* senders; int64_t edge_index_stride;
+  int32_t n_env;
+} dgppo_env_graph_hits_io;
+
+int dgppo_env_get_graph_hits(const dgppo_env_cfg* cfg, const dgppo_env_graph_hits_io* io, void* stream);
+
 /* Host-side helper: `count` obstacle records (count x 16, DGPPO_OBST_FIELDS layout) from HOST arrays center
  * (count x 2), width, height, theta (count each) = Rectangle.create (dgppo/env/obstacle.py:39-56) with the fp32
  * sin / cos and operation order of the reset kernels, so a scene can be assembled without a GPU. */

@@ -24,7 +24,13 @@ the learned safe set.  It needs an algorithm with get_Vh (dgppo, hcbfcrpo).
 Beyond the reference: `--scene PATH` evaluates on the initial states stored in a scene file
 (dgppo_fov_amd/utils/scene.py) instead of seeds -- episodes are rows [offset:epi] of the file, all of its rows when
 --epi is not given -- and `--dump-scene PATH` writes the initial states of the episodes that ran, so
-`--dump-scene s.npz` then `--scene s.npz` replays the same episodes (deterministic policy: the same numbers)."""
+`--dump-scene s.npz` then `--scene s.npz` replays the same episodes (deterministic policy: the same numbers).
+
+`--lidar-noise SIGMA` / `--lidar-dropout P` (Lidar envs with obstacles) put a sensor model between the world and the
+policy (trainer/rollout.py SensorRolloutEngine, utils/sensor.py LidarNoise seeded from --seed): the policy sees LiDAR
+ranges with Gaussian noise of std SIGMA world units and beams dropped with probability P, while the env steps, the
+rewards and the costs stay the true ones.  Either flag routes the evaluation through that loop; the summary line then
+names both values."""
 import argparse
 import os
 
@@ -62,6 +68,14 @@ def test(args):
                      max_grad_norm=2.0, seed=cfg["seed"], use_rnn=cfg.get("use_rnn", True),
                      rnn_layers=cfg.get("rnn_layers", 1), use_lstm=cfg.get("use_lstm", False),
                      batch_size=cfg.get("batch_size", 16384), rnn_step=cfg.get("rnn_step", 16), device=dev)
+    sensed = args.lidar_noise is not None or args.lidar_dropout is not None
+    if sensed:  # refused before anything is loaded or run
+        sigma, drop = args.lidar_noise or 0.0, args.lidar_dropout or 0.0
+        if env._obstacle_fields() == 0 or env.n_obs == 0 or not hasattr(env, "lidar_scan"):
+            raise SystemExit(f"--lidar-noise / --lidar-dropout need a LiDAR env with obstacles; {type(env).__name__} "
+                             f"with {env.n_obs} obstacles has no LiDAR")
+        if not sigma >= 0.0 or not 0.0 <= drop <= 1.0:
+            raise SystemExit(f"--lidar-noise must be >= 0 and --lidar-dropout in [0, 1], got {sigma} and {drop}")
     if args.cbf is not None and args.video and not args.no_video:  # refused before anything is loaded or run
         if not callable(getattr(algo, "get_Vh", None)):
             raise SystemExit(f"--cbf needs an algorithm with get_Vh; {cfg['algo']} has none")
@@ -94,8 +108,16 @@ def test(args):
     if scene is not None:  # episodes are rows [offset:epi] of the file
         cut = lambda t: None if t is None else t[args.offset:args.epi]  # noqa: E731
         init_state = type(scene)(*(cut(part) for part in scene))
-    eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
-                        mode=mode, init_state=init_state)
+    if sensed:
+        from dgppo_fov_amd.trainer.rollout import SensorRolloutEngine
+        from dgppo_fov_amd.utils.sensor import LidarNoise
+
+        sensor = LidarNoise(sigma, drop, args.seed, sense_range=float(env.params["comm_radius"]))
+        eng = SensorRolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset,
+                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state)
+    else:
+        eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
+                            mode=mode, init_state=init_state)
     roll = eng.run(args.seed)
     if args.dump_scene is not None:
         from dgppo_fov_amd.utils.scene import save_scene
@@ -111,7 +133,7 @@ def test(args):
     safe_mean, safe_std = (1 - is_unsafe).mean(), (1 - is_unsafe).std()
     print(f"reward: {np.mean(rewards):.3f}, min/max reward: {np.min(rewards):.3f}/{np.max(rewards):.3f}, "
           f"cost: {np.mean(costs):.3f}, min/max cost: {np.min(costs):.3f}/{np.max(costs):.3f}, "
-          f"safe_rate: {safe_mean * 100:.3f}%")
+          f"safe_rate: {safe_mean * 100:.3f}%" + (f", lidar noise: {sigma:g}, lidar dropout: {drop:g}" if sensed else ""))
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(f"{env.num_agents},{args.epi},{env.max_episode_steps},{env.area_size},{env.params['n_obs']},"
@@ -138,7 +160,7 @@ def test(args):
     return dict(reward=float(np.mean(rewards)), cost=float(np.mean(costs)), safe_rate=float(safe_mean))
 
 
-def main():
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--path", type=str, required=True)
     parser.add_argument("--no-video", action="store_true", default=False)
@@ -162,7 +184,14 @@ def main():
     parser.add_argument("--dpi", type=int, default=100)
     parser.add_argument("--cbf", type=int, default=None, metavar="AGENT")  # with --video: the Vh field of this agent
     parser.add_argument("--cbf-grid", type=int, default=32, metavar="G")
-    return test(parser.parse_args())
+    # sensor in the loop (Lidar envs): range noise std in world units, per-beam dropout probability
+    parser.add_argument("--lidar-noise", type=float, default=None, metavar="SIGMA")
+    parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P")
+    return parser
+
+
+def main():
+    return test(build_parser().parse_args())
 
 
 if __name__ == "__main__":
