@@ -172,6 +172,26 @@ class EnvGraphHitsIO(ctypes.Structure):  # dgppo_env_graph_hits_io
     ]
 
 
+OBSERVE_NOISE, OBSERVE_DROPOUT = 1, 2  # include/dgppo_hip.h DGPPO_OBSERVE_*
+
+
+class LidarObserveIO(ctypes.Structure):  # dgppo_lidar_observe_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("goal", c_f32p), ("goal_stride", ctypes.c_int64),
+        ("obstacles", c_f32p), ("obstacles_stride", ctypes.c_int64),
+        ("ray_dirs", c_f32p),
+        ("nodes", c_f32p), ("nodes_stride", ctypes.c_int64),
+        ("edges", c_f32p), ("edges_stride", ctypes.c_int64),
+        ("out_states", c_f32p), ("out_states_stride", ctypes.c_int64),
+        ("receivers", c_f32p), ("senders", c_f32p), ("edge_index_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32), ("flags", ctypes.c_int32),
+        ("env_offset", ctypes.c_int64), ("t", ctypes.c_int64),
+        ("seed", ctypes.c_uint64), ("seed_ptr", c_f32p),
+        ("noise_scale", ctypes.c_float), ("drop_below", ctypes.c_float),
+    ]
+
+
 RENDER_FOV = 1  # include/dgppo_hip.h DGPPO_RENDER_FOV
 
 
@@ -407,6 +427,7 @@ SIGNATURES = {
     "dgppo_lidar_hits": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarHitsIO), ctypes.c_void_p]),
     "dgppo_env_get_graph_hits": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphHitsIO),
                                                 ctypes.c_void_p]),
+    "dgppo_lidar_observe": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO), ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),

@@ -28,7 +28,7 @@ from ..env.base import MultiAgentEnv
 from ..nn import kernels as K
 from ..nn.layers import GraphBatch
 from ..trainer.data import Rollout
-from ..trainer.rollout import RolloutEngine
+from ..trainer.rollout import NoisyLidarRolloutEngine, RolloutEngine
 from .module.nets import ActorNet, VhNet, VlNet
 
 
@@ -137,10 +137,14 @@ class DGPPO:
                  coef_ent: float = 1e-2, max_grad_norm: float = 2.0, seed: int = 0, use_rnn: bool = True,
                  rnn_layers: int = 1, rnn_step: int = 16, use_lstm: bool = False, alpha: float = 10.0,
                  cbf_eps: float = 1e-2, cbf_weight: float = 1.0, train_steps: int = int(1e5),
-                 cbf_schedule: bool = True, device=None, **kwargs):
+                 cbf_schedule: bool = True, device=None, lidar_noise: Optional[float] = None,
+                 lidar_dropout: Optional[float] = None, **kwargs):
         if rnn_layers < 1:
             raise ValueError(f"rnn_layers {rnn_layers} < 1")
         self._env = env
+        # training under the LiDAR sensor model (trainer/rollout.py NoisyLidarRolloutEngine): with either value given,
+        # collect and det_rollout return the OBSERVED graphs, so the actor, Vl and Vh all fit what the robots see
+        self.sensor = self._sensor_model(env, lidar_noise, lidar_dropout)
         self.device = torch.device(device) if device is not None else env.device
         self._node_dim, self._edge_dim, self._action_dim, self._n_agents = node_dim, edge_dim, action_dim, n_agents
         self.actor_gnn_layers, self.Vl_gnn_layers, self.Vh_gnn_layers = actor_gnn_layers, Vl_gnn_layers, Vh_gnn_layers
@@ -188,6 +192,25 @@ class DGPPO:
         self.trace: Optional[dict] = None  # set to {} to record update intermediates (parity tests)
         self.key = np.random.default_rng(seed)
         self.np_rng = np.random.default_rng(seed)
+
+    SENSOR_OK = True  # False: the algorithm reads the true state off the rollout's graphs (HCBF-CRPO's get_cost)
+
+    @classmethod
+    def _sensor_model(cls, env, lidar_noise, lidar_dropout):
+        """(sigma, dropout) of the training-time sensor model, or None when neither is given.  ValueError for an
+        algorithm or env that cannot train under it and for values outside LidarNoise's domain."""
+        if lidar_noise is None and lidar_dropout is None:
+            return None
+        from ..utils.sensor import LidarNoise
+
+        if not cls.SENSOR_OK:
+            raise ValueError(f"{cls.__name__} evaluates env.get_cost on the rollout's graphs, which must be the true "
+                             "ones: lidar_noise / lidar_dropout are not supported (dgppo, informarl, informarl_lagr are)")
+        if env.ENGINE in env._VMAS_ENGINES or env._obstacle_fields() == 0 or env.n_obs == 0:
+            raise ValueError(f"lidar_noise / lidar_dropout need a LiDAR env with obstacles; {type(env).__name__} with "
+                             f"{env.n_obs} obstacles has no LiDAR")
+        model = LidarNoise(lidar_noise or 0.0, lidar_dropout or 0.0, 0, sense_range=float(env.params["comm_radius"]))
+        return model.sigma, model.dropout
 
     # ---- reference properties ------------------------------------------------------------------
     @property
@@ -293,9 +316,14 @@ class DGPPO:
     def _engine(self, n_env: int, mode: int) -> RolloutEngine:
         k = (n_env, mode)
         if k not in self._engines:
-            eng = RolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
-                                env_offset=self.rank * n_env, actor=self.actor, mode=mode,
-                                lanes=self._rollout_lanes(n_env))
+            if self.sensor is not None:
+                eng = NoisyLidarRolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
+                                              env_offset=self.rank * n_env, actor=self.actor, mode=mode,
+                                              sigma=self.sensor[0], dropout=self.sensor[1])
+            else:
+                eng = RolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
+                                    env_offset=self.rank * n_env, actor=self.actor, mode=mode,
+                                    lanes=self._rollout_lanes(n_env))
             if os.environ.get("DGPPO_NO_GRAPH", "0") != "1":
                 eng.capture()
             self._engines[k] = eng
@@ -311,11 +339,18 @@ class DGPPO:
         if n_env is None:
             n_env = len(key) if hasattr(key, "__len__") else 128
         seed = int(np.asarray(key).reshape(-1)[0]) if hasattr(key, "__len__") else int(key)
-        return self._engine(n_env, RolloutEngine.MODE_SAMPLE).run(seed)
+        return self._run_engine(n_env, RolloutEngine.MODE_SAMPLE, seed)
 
     def det_rollout(self, n_env: int, key: int) -> Rollout:
         """test_rollout with the deterministic policy; the same aliasing as collect() applies."""
-        return self._engine(n_env, RolloutEngine.MODE_DET).run(key)
+        return self._run_engine(n_env, RolloutEngine.MODE_DET, key)
+
+    def _run_engine(self, n_env: int, mode: int, key: int) -> Rollout:
+        """One rollout of the cached engine; under a sensor model the observed Rollout (graph and next_graph what the
+        policy saw, rewards and costs the true ones)."""
+        eng = self._engine(n_env, mode)
+        roll = eng.run(key)
+        return roll if self.sensor is None else eng.observed_rollout()
 
     # ---- update ------------------------------------------------------------------------------
     def _env_ids(self, batches):

@@ -14,6 +14,8 @@ from .informarl import InforMARL
 
 
 class HCBFCRPO(InforMARL):
+    SENSOR_OK = False  # Vh is env.get_cost of the rollout's graphs: they must be the true ones
+
     @property
     def config(self) -> dict:
         c = dict(super(InforMARL, self).config)

@@ -26,6 +26,7 @@
 
 #include "../../include/dgppo_hip.h"
 #include "math32.h"
+#include "noise.h"
 #include "vmas.h"
 
 #pragma clang fp contract(off)
@@ -3079,6 +3080,27 @@ __global__ __launch_bounds__(64) void lidar_hits_kernel(dgppo_env_cfg cfg, dgppo
   }
 }
 
+// the graph of the agent rows (cv.nxt), goal rows (cv.cur + n SD) and hit rows (cv.hits) staged in LDS
+template <int ENGINE, int GOAL, int SD, int BLOCK, class IO, class D>
+__device__ __forceinline__ void graph_of_staged_hits(const dgppo_env_cfg& cfg, const IO& io, const D& d, const Carve& cv,
+                                                     float* lds, int64_t env) {
+  const int tid = threadIdx.x;
+  const float* nxt = lds + cv.nxt;
+  const float* goal = lds + cv.cur + d.n * SD;
+  GraphOut out;
+  out.nodes = io.nodes + env * io.nodes_stride;
+  out.edges = io.edges + env * io.edges_stride;
+  out.states = io.out_states + env * io.out_states_stride;
+  out.recv = io.receivers + env * io.edge_index_stride;
+  out.send = io.senders + env * io.edge_index_stride;
+  if constexpr (ENGINE == DGPPO_ENGINE_OMNI) {
+    write_graph_omni(cfg, d.n, d.k, true, nxt, goal, lds + cv.hits, out, tid, BLOCK);
+  } else {
+    const bool vec4 = ((io.edges_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(io.edges) & 15) == 0);
+    write_graph<ENGINE, GOAL, SD>(cfg, d, nxt, goal, lds + cv.hits, out, vec4, tid, BLOCK);
+  }
+}
+
 // dgppo_env_get_graph_hits: env_graph_kernel with the hit rows loaded from the caller's (n, k, 2) tensor into
 // lds + cv.hits instead of ray-cast; then the same write_graph / write_graph_omni.  No obstacles are read.
 template <int ENGINE, int GOAL, int SD, int BLOCK>
@@ -3100,18 +3122,90 @@ __global__ __launch_bounds__(BLOCK) void env_graph_hits_kernel(dgppo_env_cfg cfg
   }
   for (int idx = tid; idx < n * k * 2; idx += BLOCK) lds[cv.hits + idx] = ht[idx];
   __syncthreads();
-  GraphOut out;
-  out.nodes = io.nodes + env * io.nodes_stride;
-  out.edges = io.edges + env * io.edges_stride;
-  out.states = io.out_states + env * io.out_states_stride;
-  out.recv = io.receivers + env * io.edge_index_stride;
-  out.send = io.senders + env * io.edge_index_stride;
-  if constexpr (ENGINE == DGPPO_ENGINE_OMNI) {
-    write_graph_omni(cfg, n, k, true, nxt, goal, lds + cv.hits, out, tid, BLOCK);
-  } else {
-    const bool vec4 = ((io.edges_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(io.edges) & 15) == 0);
-    write_graph<ENGINE, GOAL, SD>(cfg, d, nxt, goal, lds + cv.hits, out, vec4, tid, BLOCK);
+  graph_of_staged_hits<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
+}
+
+// dgppo_lidar_observe: scan | LidarNoise | hits | graph in one launch, one workgroup per env.  The beams of all agents
+// are cast by lidar_alpha_kernel's arithmetic into LDS (the alphas in the carve's hpt region, their sort keys in its
+// alpha region), the sensor model (utils/sensor.py LidarNoise.__call__, op for op) edits each alpha as it is made,
+// lidar_hits_kernel's counting rank puts the top-k hit points into lds + cv.hits, and graph_of_staged_hits writes
+// the graph.  Every input row is staged before the first store.
+template <int ENGINE, int GOAL, int SD, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg, dgppo_lidar_observe_io io) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Dims<0, -1, 0, 0> d(cfg);
+  const int n = d.n, O = d.O, R = d.R, k = d.k;
+  const Carve cv(n, SD, O, R, k, true);
+  const int tid = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  float* nxt = lds + cv.nxt;
+  float* goal = lds + cv.cur + n * SD;
+  const float* ag = io.agent + env * io.agent_stride;
+  const float* gl = io.goal + env * io.goal_stride;
+  const float* ob = io.obstacles + env * io.obstacles_stride;
+  for (int idx = tid; idx < n * SD; idx += BLOCK) {
+    nxt[idx] = ag[idx];
+    goal[idx] = gl[idx];
   }
+  for (int idx = tid; idx < O * DGPPO_OBST_FIELDS; idx += BLOCK) lds[cv.obst + idx] = ob[idx];
+  __syncthreads();
+  stage_edge_vectors(O, lds, cv, tid, BLOCK);
+  for (int i = tid; i < n; i += BLOCK) agent_is_inside(O, lds, cv, SD, i);
+  __syncthreads();
+  const float* obst = lds + cv.obst;
+  const float* evec = lds + cv.evec;
+  float* alpha = lds + cv.hpt;                                     // (n, R)
+  uint64_t* keys = reinterpret_cast<uint64_t*>(lds + cv.alpha);    // (n, R)
+  const uint64_t seed = io.seed_ptr ? *io.seed_ptr : io.seed;
+  const uint64_t stream = ((uint64_t)1 << 62) + 2 * (uint64_t)io.t;  // LidarNoise.STREAM_BASE + 2 t (+ 1: dropout)
+  const int64_t e0 = (io.env_offset + env) * n * R;
+#pragma unroll 1
+  for (int q = tid; q < n * R; q += BLOCK) {
+    const int i = q / R, r = q - i * R;
+    const float sx = nxt[i * SD + 0], sy = nxt[i * SD + 1];
+    const float ex = sx + io.ray_dirs[2 * r + 0];
+    const float ey = sy + io.ray_dirs[2 * r + 1];
+    const float ax = sx - ex, ay = sy - ey;
+    float a = 0.0f;
+#pragma unroll 1
+    for (int o = 0; o < O; ++o) {
+      const float ao = rect_raytrace(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
+      a = o == 0 ? ao : min_nan(a, ao);
+    }
+    a = a * (1.0f - lds[cv.isin + i]);
+    float seen = a;
+    if (io.flags & DGPPO_OBSERVE_NOISE) {
+      const float x = a + noise::normal_at(e0 + q, seed, stream) * io.noise_scale;
+      const float noisy = x != x ? x : fmaxf(x, 0.0f);  // torch.clamp_min
+      seen = a <= 1.0f ? noisy : a;
+    }
+    if (io.flags & DGPPO_OBSERVE_DROPOUT) {
+      const bool drop = (noise::normal_at(e0 + q, seed, stream + 1) < io.drop_below) & !(a != a);
+      seen = drop ? 1e6f : seen;
+    }
+    alpha[q] = seen;
+    keys[q] = sort_key(seen, r);
+  }
+  __syncthreads();
+  float* hits = lds + cv.hits;
+#pragma unroll 1
+  for (int q = tid; q < n * R; q += BLOCK) {
+    const int i = q / R, r = q - i * R;
+    const uint64_t* row = keys + i * R;
+    const uint64_t key = row[r];
+    int rank = 0;
+    for (int j = 0; j < R; ++j) rank += row[j] < key ? 1 : 0;
+    if (rank < k) {
+      const float a = alpha[q];
+      const float sx = nxt[i * SD + 0], sy = nxt[i * SD + 1];
+      const float ex = sx + io.ray_dirs[2 * r + 0];
+      const float ey = sy + io.ray_dirs[2 * r + 1];
+      hits[(i * k + rank) * 2 + 0] = sx + (ex - sx) * a;
+      hits[(i * k + rank) * 2 + 1] = sy + (ey - sy) * a;
+    }
+  }
+  __syncthreads();
+  graph_of_staged_hits<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
 }
 
 // ---- reference env variants ------------------------------------------------------------------
@@ -4380,6 +4474,27 @@ extern "C" int dgppo_env_get_graph_hits(const dgppo_env_cfg* cfg, const dgppo_en
     if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
       hipLaunchKernelGGL((env_graph_hits_kernel<E::ENGINE, E::GOAL, E::SD, 128>), dim3((unsigned)io->n_env), dim3(128),
                          shmem, s, *cfg, *io);
+  });
+  return (int)hipGetLastError();
+}
+
+extern "C" int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream) {
+  if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (cfg->variant != DGPPO_VARIANT_NONE) return DGPPO_EINVAL;  // LidarLine: the three launches (env.observe chains them)
+  if (io->t < 0 || io->env_offset < 0 || (io->flags & ~(DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT)))
+    return DGPPO_EINVAL;
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->goal || !io->obstacles || !io->ray_dirs || !io->nodes || !io->edges || !io->out_states ||
+      !io->receivers || !io->senders)
+    return DGPPO_EINVAL;
+  const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k, true);
+  const size_t shmem = (size_t)cv.total * sizeof(float);
+  if (shmem > 64 * 1024) return DGPPO_EINVAL;
+  visit_engine_goal(*cfg, [&](auto e) {
+    using E = decltype(e);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
+      hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128>), dim3((unsigned)io->n_env), dim3(128),
+                         shmem, (hipStream_t)stream, *cfg, *io);
   });
   return (int)hipGetLastError();
 }

@@ -529,6 +529,69 @@ class MultiAgentEnv(ABC):
                                            g.receivers, g.senders)
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
+    def observe(self, state, t: int, *, sigma: float, dropout: float, seed, env_offset: int = 0,
+                out: Optional[GraphsTuple] = None) -> GraphsTuple:
+        """The OBSERVED graph of the true `state` (get_graph's tuple, obstacles required) at step `t` under the
+        range-noise / beam-dropout sensor model of utils/sensor.py, in one HIP launch (torch.ops.dgppo.lidar_observe):
+        bit for bit `get_graph(state, lidar_data=lidar_hits(agent, LidarNoise(sigma, dropout, seed,
+        sense_range=comm_radius)(lidar_scan(agent, obstacle), t)))`, with env b's draws taken at row env_offset + b of
+        the noise streams (ranks of a multi-GPU run pass rank * n_env).  seed: an int, or a 1-element int64 device
+        tensor read at run time (replays of a captured rollout draw new noise).  sigma = dropout = 0 is the true
+        graph.  `out` may be the graph whose env_states are `state`.  LidarLine runs the chained launches instead of
+        the fused kernel (same results)."""
+        from ..utils.sensor import LidarNoise
+
+        what = "observe"
+        self._require_lidar(what)
+        sense_range = float(self._params["comm_radius"])
+        model = LidarNoise(sigma, dropout, 0, sense_range=sense_range)  # checks sigma and dropout; Phi^-1(dropout)
+        t, env_offset = int(t), int(env_offset)
+        if t < 0 or env_offset < 0:
+            raise ValueError(f"observe: t and env_offset must be >= 0, got {t} and {env_offset}")
+        agent, goal, third, B = self.state_rows(state, what + ": state")
+        dev = agent.device if out is None else out.nodes.device
+        n, sd = self._num_agents, self.state_dim
+        agent = self._sensor_arg(what, "state.agent", agent, (B, n, sd), dev)
+        goal = self._sensor_arg(what, "state.goal", goal, (B, self.num_goals, sd), dev)
+        third = self._sensor_arg(what, "state.obstacle", third, (B, self.n_obs, self._obstacle_fields()), dev)
+        tkey = seed if isinstance(seed, torch.Tensor) else None
+        if tkey is not None and (tkey.device != dev or tkey.numel() != 1 or tkey.dtype != torch.int64):
+            raise ValueError("observe: a tensor seed must be a 1-element int64 tensor on the env's device")
+        _lib.require_gpu(dev, "env.observe")
+        g = self.empty_graph((B,), dev) if out is None else out
+        if g.states.dim() != 3 or g.states.shape[0] != B:
+            raise ValueError(f"observe: out must hold {B} graphs")
+        if self.cfg.variant != _lib.DGPPO_VARIANT_NONE:
+            return self._observe_chained(model, agent, goal, third, t, seed, env_offset, g)
+        iseed = 0 if tkey is not None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        flags = (_lib.OBSERVE_NOISE if model.sigma > 0.0 else 0) | (_lib.OBSERVE_DROPOUT if model.dropout > 0.0 else 0)
+        torch.ops.dgppo.lidar_observe(self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
+                                      iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t,
+                                      model.sigma / sense_range, model._drop_below, flags, g.nodes, g.edges, g.states,
+                                      g.receivers, g.senders)
+        return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
+
+    def _observe_chained(self, model, agent, goal, third, t, seed, env_offset, g) -> GraphsTuple:
+        """observe by the three launches with LidarNoise's arithmetic between them (the variant envs)."""
+        from ..nn import kernels as K
+        from ..utils.sensor import NO_RETURN
+
+        alpha = self.lidar_scan(agent, third)
+        B = alpha.shape[0]
+        seen = alpha
+        if model.sigma > 0.0 or model.dropout > 0.0:
+            kw = dict(seed_tensor=seed) if isinstance(seed, torch.Tensor) else dict(seed=int(seed))
+            z = torch.empty((env_offset + B,) + tuple(alpha.shape[1:]), dtype=torch.float32, device=alpha.device)
+            if model.sigma > 0.0:
+                K.normal_(z, stream_id=model.STREAM_BASE + 2 * t, **kw)
+                noisy = torch.clamp_min(alpha + z[env_offset:] * (model.sigma / model.sense_range), 0.0)
+                seen = torch.where(alpha <= 1.0, noisy, alpha)
+            if model.dropout > 0.0:
+                K.normal_(z, stream_id=model.STREAM_BASE + 2 * t + 1, **kw)
+                drop = (z[env_offset:] < model._drop_below) & ~torch.isnan(alpha)
+                seen = torch.where(drop, torch.full_like(alpha, NO_RETURN), seen)
+        return self._get_graph_hits((agent, goal, third), g, self.lidar_hits(agent, seen))
+
     def get_reward(self, graph: GraphsTuple, action: torch.Tensor) -> torch.Tensor:
         """Reward (B,) of taking `action` in `graph` (lidar_spread.py:35-52, ...): the step kernel evaluates it."""
         return self.step(graph, action).reward

@@ -15,6 +15,7 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::lidar_scan     dgppo_lidar_scan     the per-beam alphas of get_lidar, env/utils.py:115-130
   dgppo::lidar_hits     dgppo_lidar_hits     alphas -> top-k hit points, env/utils.py:66-79
   dgppo::env_get_graph_hits dgppo_env_get_graph_hits  get_graph(state, lidar_data), lidar_env/base.py:227-271
+  dgppo::lidar_observe  dgppo_lidar_observe  scan, LidarNoise, hits and graph fused: the observed graph of a true state
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
@@ -339,6 +340,45 @@ def env_get_graph_hits(cfg: int, agent: Tensor, goal: Tensor, hits: Tensor, node
 
 @env_get_graph_hits.register_fake
 def _env_get_graph_hits_fake(cfg, agent, goal, hits, nodes, edges, states, receivers, senders) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::lidar_observe", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
+def lidar_observe(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_dirs: Tensor, key: Optional[Tensor],
+                  seed: int, env_offset: int, t: int, noise_scale: float, drop_below: float, flags: int,
+                  nodes: Tensor, edges: Tensor, states: Tensor, receivers: Tensor, senders: Tensor) -> None:
+    """The observed graph of B true states under the LidarNoise sensor model, one launch: lidar_scan, the model
+    (utils/sensor.py: flags = OBSERVE_NOISE | OBSERVE_DROPOUT, noise_scale = sigma / sense_range, drop_below =
+    Phi^-1(dropout)), lidar_hits and env_get_graph_hits fused.  The draws of beam (b, i, r) are the Philox normals of
+    element ((env_offset + b) n + i) R + r under (seed or *key) and the streams of step t.  `key`: optional 1-element
+    int64 device tensor read at run time (hipGraph replays)."""
+    _lib.require_gpu(states.device, "dgppo::lidar_observe")
+    io = _lib.LidarObserveIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.goal, io.goal_stride = _p(goal), _stride(goal, 2)
+    io.obstacles, io.obstacles_stride = _p(obstacles), _stride(obstacles, 2)
+    io.ray_dirs = _p(ray_dirs)
+    io.nodes, io.nodes_stride = _p(nodes), _stride(nodes, 2)
+    io.edges, io.edges_stride = _p(edges), _stride(edges, 2)
+    io.out_states, io.out_states_stride = _p(states), _stride(states, 2)
+    io.receivers, io.senders = _p(receivers), _p(senders)
+    io.edge_index_stride = _stride(receivers, 1)
+    io.n_env, io.flags = int(agent.shape[0]), int(flags)
+    io.env_offset, io.t = int(env_offset), int(t)
+    if key is not None:
+        if key.device != states.device or key.numel() != 1 or key.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("tensor key must be a 1-element int64 tensor on the env's device")
+        io.seed, io.seed_ptr = 0, key.data_ptr()
+    else:
+        io.seed, io.seed_ptr = int(seed) & 0xFFFFFFFFFFFFFFFF, None
+    io.noise_scale, io.drop_below = float(noise_scale), float(drop_below)
+    _lib.check(_lib.load().dgppo_lidar_observe(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
+               "dgppo_lidar_observe")
+
+
+@lidar_observe.register_fake
+def _lidar_observe_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
+                        flags, nodes, edges, states, receivers, senders) -> None:
     return None
 
 

@@ -209,9 +209,10 @@ class RolloutEngine:
             self._run()
         return self.rollout()
 
-    def rollout(self) -> Rollout:
-        """(B, T, ...) views of the time-major buffers (Rollout of dgppo/trainer/data.py)."""
-        b, T = self.buf, self.T
+    def rollout(self, graphs: Optional[GraphsTuple] = None) -> Rollout:
+        """(B, T, ...) views of the time-major buffers (Rollout of dgppo/trainer/data.py).  graphs: another (T+1, B)
+        graph buffer to take `graph` and `next_graph` from (default: the engine's true graphs)."""
+        b, T = self.buf if graphs is None else graphs, self.T
 
         def view(sl):
             tr = lambda x: x[sl].transpose(0, 1)  # noqa: E731
@@ -289,3 +290,73 @@ class SensorRolloutEngine(RolloutEngine):
         tr = lambda x: x.transpose(0, 1)  # noqa: E731
         return self.env._assemble(tr(b.nodes), tr(b.edges), tr(b.states), tr(b.receivers), tr(b.senders),
                                   self.obstacles)
+
+
+class NoisyLidarRolloutEngine(RolloutEngine):
+    """RolloutEngine under the LidarNoise sensor model (utils/sensor.py), the sensor one fused launch per step
+    (env.observe, torch.ops.dgppo.lidar_observe), so the whole rollout captures into a hipGraph: what training under
+    the sensor model runs.  SensorRolloutEngine(sensor=LidarNoise(sigma, dropout, seed=key)) is its definition; this
+    engine gives the same bits.
+
+    Per step t: obs[t] = env.observe(true state_t, t) into a time-major buffer of T + 1 observed graphs; the actor acts
+    on obs[t]; env.step_into advances the TRUE graph and writes the true reward and cost.  After the loop obs[T] is
+    observed from the final true state (the update's final-value graph).  The noise seed is the engine's key tensor --
+    a replay with a new key draws new noise -- under the sensor's stream ids (2^62 + 2t, + 1), which cannot collide
+    with the policy's (env_offset << 32) | t; env b's beams draw at row env_offset + b.
+
+    `run` returns the true Rollout; `observed_rollout()` the Rollout the algorithms train on: graph and next_graph
+    the observed ones, every other field the true run's.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env
+    with obstacles."""
+
+    def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
+                 actor=None, mode: int = RolloutEngine.MODE_SAMPLE, sigma: float = 0.0, dropout: float = 0.0,
+                 init_state=None):
+        from ..utils.sensor import LidarNoise
+
+        if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
+            raise ValueError("NoisyLidarRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
+        env._require_lidar("NoisyLidarRolloutEngine")
+        model = LidarNoise(sigma, dropout, 0, sense_range=float(env.params["comm_radius"]))  # checks both
+        self.sigma, self.dropout = model.sigma, model.dropout
+        super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
+        self.obs = env.empty_graph((self.T + 1, self.B), self.device)  # time-major, like buf
+
+    def _observed_at(self, t: int) -> GraphsTuple:
+        b = self.obs
+        return self.env._assemble(b.nodes[t], b.edges[t], b.states[t], b.receivers[t], b.senders[t], self.obstacles)
+
+    def _batch(self, t: int, sl=slice(None)) -> GraphBatch:  # the actor's input: the observed graph of step t
+        b = self.obs
+        return GraphBatch.of(self.env, b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl])
+
+    def _observe(self, t: int):
+        env, n = self.env, self.env.num_agents
+        s = self.buf.states[t]
+        env.observe((s[:, :n], s[:, n:n + env.num_goals], self.obstacles), t, sigma=self.sigma, dropout=self.dropout,
+                    seed=self.key, env_offset=self.env_offset, out=self._observed_at(t))
+
+    def _run(self):
+        env = self.env
+        if self.init_state is not None:
+            cur = env.get_graph(self.init_state, out=self.graph_at(0))
+        else:
+            cur = env.reset(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
+                            obstacles_out=self.obstacles)
+        for t in range(self.T):
+            self._observe(t)
+            self._act(t)
+            cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
+        self._observe(self.T)
+
+    @property
+    def observed(self) -> GraphsTuple:
+        """The T + 1 observed graphs, batch shape (B, T + 1): views of the time-major buffer."""
+        b = self.obs
+        tr = lambda x: x.transpose(0, 1)  # noqa: E731
+        return self.env._assemble(tr(b.nodes), tr(b.edges), tr(b.states), tr(b.receivers), tr(b.senders),
+                                  self.obstacles)
+
+    def observed_rollout(self) -> Rollout:
+        """The last run as the algorithms read it: graph = obs[0:T] and next_graph = obs[1:T+1] as (B, T) views,
+        actions, carries, log_pis, rewards, costs and dones the true run's."""
+        return self.rollout(self.obs)

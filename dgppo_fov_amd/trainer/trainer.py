@@ -14,7 +14,7 @@ import torch.distributed as dist
 
 from ..algo.dgppo import DGPPO
 from ..env.base import MultiAgentEnv
-from ..trainer.rollout import RolloutEngine
+from ..trainer.rollout import NoisyLidarRolloutEngine, RolloutEngine
 from .utils import eval_info
 
 
@@ -67,8 +67,14 @@ class Trainer:
         """test_rollout with the deterministic policy on n_env_test envs (trainer.py:85-116)."""
         assert self.n_env_test <= 1_000, "n_env_test must be less than or equal to 1_000"
         if self._test_engine is None:
-            self._test_engine = RolloutEngine(self.env_test, self.n_env_test, self.env_test.max_episode_steps,
-                                              self.algo.device, actor=self.algo.actor, mode=RolloutEngine.MODE_DET)
+            sensor = getattr(self.algo, "sensor", None)
+            if sensor is not None:  # trained under a sensor model: the true costs under sensed control
+                self._test_engine = NoisyLidarRolloutEngine(
+                    self.env_test, self.n_env_test, self.env_test.max_episode_steps, self.algo.device,
+                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sigma=sensor[0], dropout=sensor[1])
+            else:
+                self._test_engine = RolloutEngine(self.env_test, self.n_env_test, self.env_test.max_episode_steps,
+                                                  self.algo.device, actor=self.algo.actor, mode=RolloutEngine.MODE_DET)
         r = self._test_engine.run(key)
         return eval_info(r.rewards, r.costs)
 

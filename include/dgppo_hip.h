@@ -264,6 +264,44 @@ typedef struct dgppo_env_graph_hits_io {
 
 int dgppo_env_get_graph_hits(const dgppo_env_cfg* cfg, const dgppo_env_graph_hits_io* io, void* stream);
 
+/* dgppo_lidar_observe: the OBSERVED graph of the true state under the range-noise / beam-dropout sensor model, one
+ * launch: dgppo_lidar_scan, the sensor model on every beam, dgppo_lidar_hits and dgppo_env_get_graph_hits fused
+ * (same device functions, same bits as the three launches with the sensor between them).  `agent`, `goal`,
+ * `obstacles`, `ray_dirs` and the outputs as in dgppo_env_graph_io (third = obstacles).  The sensor model per beam,
+ * element index e = ((env_offset + env) * n + agent) * R + ray, draws z = the standard normal of dgppo_normal at
+ * (element e, seed, stream_id):
+ *   DGPPO_OBSERVE_NOISE    where alpha <= 1: alpha' = max(alpha + z * noise_scale, 0) (NaN stays NaN), z from stream
+ *                          2^62 + 2 t; every other alpha passes.  noise_scale = (float)(sigma / sense_range).
+ *   DGPPO_OBSERVE_DROPOUT  then alpha' = 1e6 where z2 < drop_below and alpha is not NaN, z2 from stream 2^62 + 2 t + 1.
+ *                          drop_below = (float)Phi^-1(p), -inf / +inf for p = 0 / 1.
+ * `seed_ptr` (optional device scalar) overrides `seed` as in dgppo_env_reset_io, so a captured hipGraph draws new
+ * noise per replay.  flags = 0 is dgppo_env_get_graph by the no-culling arithmetic.  An env's outputs may alias that
+ * env's own inputs (all rows are staged before any store).  Lidar engines (double integrator, bicycle, omni) with
+ * n_obs > 0; the MPE and VMAS engines, the LidarLine variant, n_obs == 0, t < 0 and a NULL pointer return
+ * DGPPO_EINVAL without a launch; n_env == 0 returns 0.  No ABI number change (a new symbol only). */
+#define DGPPO_OBSERVE_NOISE 1
+#define DGPPO_OBSERVE_DROPOUT 2
+typedef struct dgppo_lidar_observe_io {
+  const float* agent;       int64_t agent_stride;
+  const float* goal;        int64_t goal_stride;
+  const float* obstacles;   int64_t obstacles_stride;
+  const float* ray_dirs;
+  float* nodes;             int64_t nodes_stride;
+  float* edges;             int64_t edges_stride;
+  float* out_states;        int64_t out_states_stride;
+  int32_t* receivers;       int32_t* senders; int64_t edge_index_stride;
+  int32_t n_env;
+  int32_t flags;            /* DGPPO_OBSERVE_* */
+  int64_t env_offset;
+  int64_t t;                /* the step whose streams are drawn */
+  uint64_t seed;
+  const uint64_t* seed_ptr;
+  float noise_scale;
+  float drop_below;
+} dgppo_lidar_observe_io;
+
+int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream);
+
 /* Host-side helper: `count` obstacle records (count x 16, DGPPO_OBST_FIELDS layout) from HOST arrays center
  * (count x 2), width, height, theta (count each) = Rectangle.create (dgppo/env/obstacle.py:39-56) with the fp32
  * sin / cos and operation order of the reset kernels, so a scene can be assembled without a GPU. */

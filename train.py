@@ -2,7 +2,13 @@
 MI355X kernels.  Single GPU: `python train.py --env LidarSpread -n 8 --algo dgppo --obs 3`.
 Multi-GPU (env-sharded, RCCL gradient all-reduce): `python -m torch.distributed.run --nnodes=1
 --nproc-per-node 8 --master-addr 127.0.0.1 train.py ...` -- `--n-env-train` is per GPU and
-`--batch-size` is scaled by the world size (same minibatch count per update)."""
+`--batch-size` is scaled by the world size (same minibatch count per update).
+
+Beyond the reference: `--lidar-noise SIGMA` / `--lidar-dropout P` (Lidar envs with obstacles; dgppo, informarl,
+informarl_lagr) train under the sensor model `test.py` evaluates with (utils/sensor.py LidarNoise, one fused kernel
+launch per step inside the captured rollout): the actor, Vl and Vh all see LiDAR ranges with Gaussian noise of std SIGMA
+world units and beams dropped with probability P, while the env steps, the rewards and the costs stay the true ones.
+The noise is seeded by each rollout's key, so a resumed run continues the same sequence."""
 import argparse
 import datetime
 import json
@@ -42,6 +48,10 @@ def train(args):
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = str(args.gpu)
         print(f"> Using GPU: {args.gpu}")
+    if args.lidar_noise is not None or args.lidar_dropout is not None:  # refused before the GPU is touched
+        sigma, drop = args.lidar_noise or 0.0, args.lidar_dropout or 0.0
+        if not sigma >= 0.0 or not 0.0 <= drop <= 1.0:
+            raise SystemExit(f"--lidar-noise must be >= 0 and --lidar-dropout in [0, 1], got {sigma} and {drop}")
     import torch
     import torch.distributed as dist
 
@@ -71,7 +81,8 @@ def train(args):
         batch_size=args.batch_size * world, use_rnn=not args.no_rnn, use_lstm=args.use_lstm,
         coef_ent=args.coef_ent, rnn_step=args.rnn_step, gamma=0.99, clip_eps=args.clip_eps,
         lagr_init=args.lagr_init, lr_lagr=args.lr_lagr, train_steps=args.steps,
-        cbf_schedule=not args.no_cbf_schedule, cost_schedule=args.cost_schedule, device=device)
+        cbf_schedule=not args.no_cbf_schedule, cost_schedule=args.cost_schedule, device=device,
+        lidar_noise=args.lidar_noise, lidar_dropout=args.lidar_dropout)
     if args.load_checkpoint:
         print(f"> Loading checkpoint from {args.load_checkpoint}, step {args.load_step}")
         algo.load(args.load_checkpoint, args.load_step)
@@ -113,7 +124,7 @@ def train(args):
     return done
 
 
-def main():
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--env", type=str, required=True)
     parser.add_argument("-n", "--num-agents", type=int, required=True)
@@ -159,6 +170,15 @@ def main():
     parser.add_argument("--resume", type=str, default=None, help="continue the run saved in this log dir")
     parser.add_argument("--max-minutes", type=float, default=None, help="save a resumable state and stop after")
     parser.add_argument("--log-interval", type=int, default=1, help="log.jsonl keeps every k-th update")
+    # not reference flags: train under the LiDAR sensor model test.py evaluates with (utils/sensor.py LidarNoise)
+    parser.add_argument("--lidar-noise", type=float, default=None, metavar="SIGMA",
+                        help="range noise std in world units: actor, Vl and Vh train on the observed graphs")
+    parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P", help="per-beam dropout probability")
+    return parser
+
+
+def main():
+    parser = build_parser()
     args = parser.parse_args()
     if args.load_checkpoint and args.load_step is None:
         parser.error("--load-checkpoint requires --load-step")
