@@ -357,6 +357,8 @@ def adam_multi(nets, b1=0.9, b2=0.999, eps=1e-8):
 
 
 def normal_(out, seed=0, stream_id=0, seed_tensor=None):
+    if out.numel() == 0:  # an empty tensor has no data pointer for the entry point to accept
+        return out
     _chk(_lib.load().dgppo_normal(_p(out), int(out.numel()), _p(seed_tensor), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                   int(stream_id) & 0xFFFFFFFFFFFFFFFF, _stream(out)), "dgppo_normal")
     return out

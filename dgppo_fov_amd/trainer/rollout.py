@@ -27,6 +27,20 @@ from ..utils.graph import GraphsTuple
 from .data import Rollout
 
 
+MAX_ENV_ROWS = 1 << 30  # env rows (env_offset + env) a run may address: see check_env_offset
+
+
+def check_env_offset(env_offset: int, n_env: int) -> int:
+    """The policy's sampling streams are (env_offset << 32) | t and the sensor's 2^62 + 2t (+ 1), bit 63 being the
+    generator's domain bit: they stay disjoint while env_offset < 2^30.  Raises ValueError unless
+    0 <= env_offset and env_offset + n_env <= 2^30; returns env_offset as an int."""
+    env_offset, n_env = int(env_offset), int(n_env)
+    if env_offset < 0 or env_offset + n_env > MAX_ENV_ROWS:
+        raise ValueError(f"env_offset must be >= 0 with env_offset + n_env <= 2^30 (the policy's noise streams "
+                         f"would meet the sensor's), got env_offset {env_offset}, n_env {n_env}")
+    return env_offset
+
+
 class RolloutEngine:
     MODE_RANDOM, MODE_SAMPLE, MODE_DET = -1, 1, 0
 
@@ -45,12 +59,14 @@ class RolloutEngine:
         init_state: the env's state tuple (agent, goal, obstacle) for the n_env envs (env.get_graph's argument);
         when given, every run starts from that scene instead of a reset (the key then only seeds the policy
         noise).  The fp32 device tensors are read in place on every run, so editing them between runs -- also
-        between replays of a captured engine -- runs the new scene."""
+        between replays of a captured engine -- runs the new scene.
+        env_offset: the first of this engine's n_env rows in the run's noise streams (rank * n_env on a multi-GPU
+        run); 0 <= env_offset, env_offset + n_env <= 2^30 (check_env_offset), else ValueError."""
+        self.env_offset = check_env_offset(env_offset, n_env)  # before anything is allocated
         self.env = env
         self.B = int(n_env)
         self.T = int(T or env.max_episode_steps)
         self.device = torch.device(device) if device is not None else env.device
-        self.env_offset = int(env_offset)
         self.actor = actor
         self.mode = mode if actor is not None else self.MODE_RANDOM
         B, T, n, dev = self.B, self.T, env.num_agents, self.device
@@ -302,7 +318,8 @@ class NoisyLidarRolloutEngine(RolloutEngine):
     on obs[t]; env.step_into advances the TRUE graph and writes the true reward and cost.  After the loop obs[T] is
     observed from the final true state (the update's final-value graph).  The noise seed is the engine's key tensor --
     a replay with a new key draws new noise -- under the sensor's stream ids (2^62 + 2t, + 1), which cannot collide
-    with the policy's (env_offset << 32) | t; env b's beams draw at row env_offset + b.
+    with the policy's (env_offset << 32) | t while env_offset < 2^30 (check_env_offset refuses more); env b's beams
+    draw at row env_offset + b.
 
     `run` returns the true Rollout; `observed_rollout()` the Rollout the algorithms train on: graph and next_graph
     the observed ones, every other field the true run's.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env

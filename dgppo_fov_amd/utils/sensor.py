@@ -36,8 +36,10 @@ class LidarNoise:
     `dropout`.  Non-returns and NaN pass through.  The draws come from the project's Philox generator
     (dgppo_normal) keyed (seed, stream id), the stream ids 2^62 + 2t and 2^62 + 2t + 1: reproducible for a seed,
     independent across t, and disjoint from the policy's sampling streams ((env_offset << 32) | t, env_offset <
-    2^30; bit 63 is the generator's own domain bit).  A dropout decision is `z < Phi^-1(dropout)` on a standard
-    normal z.  sigma = 0 and dropout = 0 returns the input tensor itself."""
+    2^30, which RolloutEngine enforces; bit 63 is the generator's own domain bit, so it cannot tell streams
+    apart).  A dropout decision is `z < Phi^-1(dropout)` on a standard normal z, the threshold rounded to float32.
+    sigma = 0 and dropout = 0 returns the input tensor itself.  tests/noise_ref.py restates the stream and this
+    model in float64."""
 
     STREAM_BASE = 1 << 62
 

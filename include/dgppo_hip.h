@@ -927,8 +927,11 @@ int dgppo_gather_env_steps(const dgppo_gather_field* fields, int32_t n_fields, c
 
 /* standard normal noise from Philox4x32-10 (Box-Muller); seed from *seed_ptr when non-NULL.  Element t uses
    counter (t lo, t hi, stream_id lo, stream_id hi | 0x80000000): the top bit is the noise domain, disjoint from
-   the env-reset draws (counter (draw, env, purpose, 0)) under the same key.  Replaces the threefry draws of
-   sample_action (policy.py:196-203, jax.random.normal inside tfd.Normal.sample). */
+   the env-reset draws (counter (draw, env, purpose, 0)) under the same key.  The domain bit absorbs bit 63 of
+   stream_id: streams s and s | 2^63 are the same stream, so stream ids carry 63 bits.  With ia = (word0 >> 8) + 1
+   and ib = word1 >> 8 the element is sqrt(-2 ln(ia / 2^24)) cos(2 pi ib / 2^24) evaluated in float32;
+   tests/noise_ref.py is the definition the kernels are held to.  n = 0 writes nothing.  Replaces the threefry
+   draws of sample_action (policy.py:196-203, jax.random.normal inside tfd.Normal.sample). */
 int dgppo_normal(float* out, int64_t n, const uint64_t* seed_ptr, uint64_t seed, uint64_t stream_id, void* stream);
 
 /* Library / device introspection */

@@ -105,7 +105,13 @@ def test_rollout_shards_use_disjoint_noise(cuda):
 @pytest.mark.parametrize("eid,n,obs", [("LidarSpread", 8, 3), ("LidarOmniTarget", 3, 2)])
 def test_policy_step_in_kernel_noise_bit_exact(cuda, eid, n, obs):
     """ABI 10: the fused policy step drawing its Philox noise in the kernel (noise_seed, noise_stream) gives the
-    same action, log_pi and carry bits as the step fed the buffer dgppo_normal writes for that stream."""
+    same action, log_pi and carry bits as the step fed the buffer dgppo_normal writes for that stream
+    (tests/test_normal_stream_gpu.py holds that buffer to the host reference).  Beside the first (seed, stream):
+    the largest policy stream id ((2^30 - 1) << 32 | 127) and a small one, under a seed with only its high word set
+    and the all-ones seed, which a key tensor holds as the int64 of the same bits (-1).  B = 37: at n = 8 the
+    37 * 8 * 2 = 592 noise elements cross two 256-element block boundaries of dgppo_normal and the 296 rows fill
+    19 of the policy kernel's 16-row groups, the last one half; at n = 3 (A = 3) the 333 elements cross one block
+    boundary and the 8th row group holds 2 of its 5 graphs."""
     B = 37
     env = make_env(eid, n, num_obs=obs, max_step=4, device=cuda)
     algo = make_algo("dgppo", env=env, node_dim=env.node_dim, edge_dim=env.edge_dim, state_dim=env.state_dim,
@@ -114,15 +120,26 @@ def test_policy_step_in_kernel_noise_bit_exact(cuda, eid, n, obs):
     eng.run(9)
     g = eng._batch(2)
     h = torch.randn((B * n, 64), generator=torch.Generator().manual_seed(4)).to(cuda)
-    key = torch.tensor([0x1234_5678_9ABC], dtype=torch.int64, device=cuda)
-    sid = (5 << 32) | 7
-    noise = torch.empty((B * n, env.action_dim), device=cuda)
-    K.normal_(noise, stream_id=sid, seed_tensor=key)
-    ref = algo.actor.act(g, h, 1, noise=noise)
-    got = algo.actor.act(g, h, 1, noise=torch.full_like(noise, float("nan")), noise_seed=key, noise_stream=sid)
-    torch.cuda.synchronize()
-    for a, b, what in zip(ref, got, ("action", "log_pi", "carry")):
-        assert torch.equal(a, b), what
+    assert B * n * env.action_dim > 256
+    top, ones = (((1 << 30) - 1) << 32) | 127, 0xFFFFFFFFFFFFFFFF
+    cases = [(0x1234_5678_9ABC, (5 << 32) | 7), (1 << 40, top), (1 << 40, 7), (ones, top), (ones, 7)]
+    actions = []
+    for seed, sid in cases:
+        key = torch.tensor([seed - (1 << 64) if seed >> 63 else seed], dtype=torch.int64, device=cuda)
+        noise = torch.empty((B * n, env.action_dim), device=cuda)
+        K.normal_(noise, stream_id=sid, seed_tensor=key)
+        by_value = torch.empty_like(noise)
+        K.normal_(by_value, seed=seed, stream_id=sid)
+        assert torch.equal(noise, by_value), (hex(seed), hex(sid))
+        ref = algo.actor.act(g, h, 1, noise=noise)
+        got = algo.actor.act(g, h, 1, noise=torch.full_like(noise, float("nan")), noise_seed=key, noise_stream=sid)
+        torch.cuda.synchronize()
+        for a, b, what in zip(ref, got, ("action", "log_pi", "carry")):
+            assert torch.equal(a, b), (what, hex(seed), hex(sid))
+        actions.append(got[0].clone())
+    for i in range(len(cases)):  # every (seed, stream) sampled its own actions
+        for j in range(i):
+            assert not torch.equal(actions[i], actions[j]), (cases[i], cases[j])
 
 
 @pytest.mark.parametrize("graph", [False, True])

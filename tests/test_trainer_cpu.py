@@ -33,3 +33,28 @@ def test_trainer_params_contract():
         bad.pop(k)
         with pytest.raises(AssertionError):
             Trainer._check_params(bad)
+
+
+def test_rollout_engine_refuses_env_offsets_that_meet_the_sensor_streams():
+    """env_offset + n_env <= 2^30 (the policy's streams (env_offset << 32) | t stay below the sensor's 2^62 + 2t) is
+    checked before an engine touches its env or a device -- None stands for the env here -- in every engine class."""
+    from dgppo_fov_amd.trainer.rollout import (MAX_ENV_ROWS, NoisyLidarRolloutEngine, RolloutEngine,
+                                               SensorRolloutEngine, check_env_offset)
+
+    assert MAX_ENV_ROWS == 1 << 30
+    for off, n in ((0, 1), (0, 1 << 30), ((1 << 30) - 8, 8), (5, 4096)):
+        assert check_env_offset(off, n) == off
+    bad = ((-1, 4), (1 << 30, 1), ((1 << 30) - 7, 8), (1 << 31, 4), (0, (1 << 30) + 1))
+    for off, n in bad:
+        with pytest.raises(ValueError, match="env_offset"):
+            check_env_offset(off, n)
+        with pytest.raises(ValueError, match="env_offset"):
+            RolloutEngine(None, n, 4, "cpu", env_offset=off)
+    from dgppo_fov_amd.env import make_env
+
+    env, actor = make_env("LidarSpread", 3, num_obs=2, device="cpu"), object()  # the subclasses look at both first
+    for off, n in bad:
+        with pytest.raises(ValueError, match="env_offset"):
+            SensorRolloutEngine(env, n, 4, "cpu", env_offset=off, actor=actor, sensor=lambda a, t: a)
+        with pytest.raises(ValueError, match="env_offset"):
+            NoisyLidarRolloutEngine(env, n, 4, "cpu", env_offset=off, actor=actor, sigma=0.05, dropout=0.2)
