@@ -173,6 +173,7 @@ class EnvGraphHitsIO(ctypes.Structure):  # dgppo_env_graph_hits_io
 
 
 OBSERVE_NOISE, OBSERVE_DROPOUT = 1, 2  # include/dgppo_hip.h DGPPO_OBSERVE_*
+OBSERVE_SIGHT = 4  # dgppo_lidar_observe_los only
 
 
 class LidarObserveIO(ctypes.Structure):  # dgppo_lidar_observe_io
@@ -189,6 +190,15 @@ class LidarObserveIO(ctypes.Structure):  # dgppo_lidar_observe_io
         ("env_offset", ctypes.c_int64), ("t", ctypes.c_int64),
         ("seed", ctypes.c_uint64), ("seed_ptr", c_f32p),
         ("noise_scale", ctypes.c_float), ("drop_below", ctypes.c_float),
+    ]
+
+
+class LidarSightIO(ctypes.Structure):  # dgppo_lidar_sight_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("obstacles", c_f32p), ("obstacles_stride", ctypes.c_int64),
+        ("visible", c_f32p), ("visible_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32),
     ]
 
 
@@ -428,6 +438,9 @@ SIGNATURES = {
     "dgppo_env_get_graph_hits": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(EnvGraphHitsIO),
                                                 ctypes.c_void_p]),
     "dgppo_lidar_observe": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO), ctypes.c_void_p]),
+    "dgppo_lidar_sight": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarSightIO), ctypes.c_void_p]),
+    "dgppo_lidar_observe_los": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO),
+                                               ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),

@@ -138,13 +138,18 @@ class DGPPO:
                  rnn_layers: int = 1, rnn_step: int = 16, use_lstm: bool = False, alpha: float = 10.0,
                  cbf_eps: float = 1e-2, cbf_weight: float = 1.0, train_steps: int = int(1e5),
                  cbf_schedule: bool = True, device=None, lidar_noise: Optional[float] = None,
-                 lidar_dropout: Optional[float] = None, **kwargs):
+                 lidar_dropout: Optional[float] = None, lidar_occlusion: bool = False, **kwargs):
         if rnn_layers < 1:
             raise ValueError(f"rnn_layers {rnn_layers} < 1")
         self._env = env
         # training under the LiDAR sensor model (trainer/rollout.py NoisyLidarRolloutEngine): with either value given,
         # collect and det_rollout return the OBSERVED graphs, so the actor, Vl and Vh all fit what the robots see
         self.sensor = self._sensor_model(env, lidar_noise, lidar_dropout)
+        # lidar_occlusion: obstacles also hide agents from each other in those graphs (env.observe(occlusion=True));
+        # on its own it selects the same engine with no noise and no dropout
+        self.occlusion = bool(lidar_occlusion)
+        if self.occlusion and self.sensor is None:
+            self._sensor_model(env, 0.0, 0.0)  # the same refusals as the noise flags
         self.device = torch.device(device) if device is not None else env.device
         self._node_dim, self._edge_dim, self._action_dim, self._n_agents = node_dim, edge_dim, action_dim, n_agents
         self.actor_gnn_layers, self.Vl_gnn_layers, self.Vh_gnn_layers = actor_gnn_layers, Vl_gnn_layers, Vh_gnn_layers
@@ -205,10 +210,11 @@ class DGPPO:
 
         if not cls.SENSOR_OK:
             raise ValueError(f"{cls.__name__} evaluates env.get_cost on the rollout's graphs, which must be the true "
-                             "ones: lidar_noise / lidar_dropout are not supported (dgppo, informarl, informarl_lagr are)")
+                             "ones: lidar_noise / lidar_dropout / lidar_occlusion are not supported (dgppo, informarl, "
+                             "informarl_lagr are)")
         if env.ENGINE in env._VMAS_ENGINES or env._obstacle_fields() == 0 or env.n_obs == 0:
-            raise ValueError(f"lidar_noise / lidar_dropout need a LiDAR env with obstacles; {type(env).__name__} with "
-                             f"{env.n_obs} obstacles has no LiDAR")
+            raise ValueError("lidar_noise / lidar_dropout / lidar_occlusion need a LiDAR env with obstacles; "
+                             f"{type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
         model = LidarNoise(lidar_noise or 0.0, lidar_dropout or 0.0, 0, sense_range=float(env.params["comm_radius"]))
         return model.sigma, model.dropout
 
@@ -307,6 +313,11 @@ class DGPPO:
         a, lp, h2 = self.actor.act(g, self._rows(rnn_state).reshape(B * n, -1).contiguous(), 1, noise=noise)
         return a.view(B, n, -1), lp.view(B, n), self._unrows(h2.view(B, n, -1))
 
+    @property
+    def sensed(self) -> bool:
+        """Whether collect and det_rollout return observed graphs (a sensor model, occlusion, or both)."""
+        return self.sensor is not None or self.occlusion
+
     def _rollout_lanes(self, n_env: int) -> int:
         """Env slices on separate streams (RolloutEngine lanes): DGPPO_ROLLOUT_LANES when the slices are
         whole (the engine itself keeps one stream where the fused policy step does not cover the env)."""
@@ -316,10 +327,11 @@ class DGPPO:
     def _engine(self, n_env: int, mode: int) -> RolloutEngine:
         k = (n_env, mode)
         if k not in self._engines:
-            if self.sensor is not None:
+            if self.sensed:
+                sigma, dropout = self.sensor or (0.0, 0.0)
                 eng = NoisyLidarRolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                               env_offset=self.rank * n_env, actor=self.actor, mode=mode,
-                                              sigma=self.sensor[0], dropout=self.sensor[1])
+                                              sigma=sigma, dropout=dropout, occlusion=self.occlusion)
             else:
                 eng = RolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                     env_offset=self.rank * n_env, actor=self.actor, mode=mode,
@@ -350,7 +362,7 @@ class DGPPO:
         policy saw, rewards and costs the true ones)."""
         eng = self._engine(n_env, mode)
         roll = eng.run(key)
-        return roll if self.sensor is None else eng.observed_rollout()
+        return eng.observed_rollout() if self.sensed else roll
 
     # ---- update ------------------------------------------------------------------------------
     def _env_ids(self, batches):

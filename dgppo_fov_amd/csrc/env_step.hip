@@ -3125,12 +3125,94 @@ __global__ __launch_bounds__(BLOCK) void env_graph_hits_kernel(dgppo_env_cfg cfg
   graph_of_staged_hits<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
 }
 
+// ---- line of sight between agents -----------------------------------------------------------------
+// Does the segment from (x1, y1) to (x1 - ax, y1 - ay) cross an edge of the rectangle?  rect_raytrace's per-edge
+// arithmetic and conservative `out` screen, asking "is any edge valid" instead of taking the NaN-propagating
+// minimum: det == 0 and NaN make that edge invalid (the reference's alpha is then NaN or infinite, and every
+// comparison of `valid` fails), an edge the screen proves outside [0, 1] is invalid without the divisions.
+__device__ __forceinline__ bool rect_blocks(const float* rec, const float* evec, float x1, float y1, float ax,
+                                            float ay) {
+  bool any = false;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float x3 = rec[8 + 2 * e], y3 = rec[9 + 2 * e];
+    const float exe = evec[2 * e], eye = evec[2 * e + 1];  // x4 - x3, y4 - y3
+    const float px = x1 - x3, py = y1 - y3;
+    const float det = ax * eye - ay * exe;
+    const float na = eye * px - exe * py;
+    const float nb = (-ay) * px + ax * py;
+    const float adet = fabsf(det);
+    bool valid = false;
+    if (adet > 0.0f) {
+      const float cl = adet < 1e-7f ? 1e-7f : (adet > 1e7f ? 1e7f : adet);
+      const float detc = det < 0.0f ? -cl : cl;
+      const float lim = cl * 1.001f;
+      const float ana = fabsf(na), anb = fabsf(nb);
+      const bool finite = ana <= 3.0e38f && anb <= 3.0e38f;
+      const bool neg_d = detc < 0.0f;
+      const bool out = finite && (ana > lim || anb > lim || (ana >= 1e-30f && ((na < 0.0f) != neg_d)) ||
+                                  (anb >= 1e-30f && ((nb < 0.0f) != neg_d)));
+      if (!out) {
+        const float alpha = na / detc;
+        const float beta = nb / detc;
+        valid = (alpha <= 1.0f) && (alpha >= 0.0f) && (beta <= 1.0f) && (beta >= 0.0f);
+      }
+    }
+    any = any | valid;
+  }
+  return any;
+}
+
+// is the segment from agent i to agent j (rows of `pos`, row stride ps, columns 0, 1) cut by any staged obstacle
+__device__ __forceinline__ bool pair_blocked(int O, const float* obst, const float* evec, const float* pos, int ps,
+                                             int i, int j) {
+  const float sx = pos[i * ps + 0], sy = pos[i * ps + 1];
+  const float ex = pos[j * ps + 0], ey = pos[j * ps + 1];
+  const float ax = sx - ex, ay = sy - ey;
+  bool blocked = false;
+#pragma unroll 1
+  for (int o = 0; o < O; ++o)
+    blocked = blocked | rect_blocks(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
+  return blocked;
+}
+
+// dgppo_lidar_sight: one wave per env, lanes striding over the n * n ordered (receiver, sender) pairs (any n: the
+// pair loop runs ceil(n * n / 64) passes).  Obstacle records and edge vectors staged as in lidar_alpha_kernel, the
+// agents' positions behind them.  visible[i, j] = no edge of any obstacle is valid for the segment i -> j; the
+// diagonal is 1 without a test.
+constexpr int kSightLds = kScanLds + 2 * kMaxAgents;
+__global__ __launch_bounds__(64) void lidar_sight_kernel(dgppo_env_cfg cfg, dgppo_lidar_sight_io io) {
+  __shared__ __attribute__((aligned(16))) float lds[kSightLds];
+  const int n = cfg.n_agents, O = cfg.n_obs, sd = cfg.state_dim;
+  const int lane = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  const Carve cv = scan_carve();
+  float* pos = lds + kScanLds;  // (n, 2)
+  const float* ob = io.obstacles + env * io.obstacles_stride;
+  const float* ag = io.agent + env * io.agent_stride;
+  for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) lds[cv.obst + idx] = ob[idx];
+  for (int idx = lane; idx < 2 * n; idx += 64) pos[idx] = ag[(idx >> 1) * sd + (idx & 1)];
+  __syncthreads();
+  stage_edge_vectors(O, lds, cv, lane, 64);
+  __syncthreads();
+  uint8_t* out = io.visible + env * io.visible_stride;
+#pragma unroll 1
+  for (int q = lane; q < n * n; q += 64) {
+    const int i = q / n, j = q - i * n;
+    out[q] = (i == j || !pair_blocked(O, lds + cv.obst, lds + cv.evec, pos, 2, i, j)) ? 1 : 0;
+  }
+}
+
 // dgppo_lidar_observe: scan | LidarNoise | hits | graph in one launch, one workgroup per env.  The beams of all agents
 // are cast by lidar_alpha_kernel's arithmetic into LDS (the alphas in the carve's hpt region, their sort keys in its
 // alpha region), the sensor model (utils/sensor.py LidarNoise.__call__, op for op) edits each alpha as it is made,
 // lidar_hits_kernel's counting rank puts the top-k hit points into lds + cv.hits, and graph_of_staged_hits writes
 // the graph.  Every input row is staged before the first store.
-template <int ENGINE, int GOAL, int SD, int BLOCK>
+// SIGHT (dgppo_lidar_observe_los with DGPPO_OBSERVE_SIGHT): the ordered agent pairs are tested by lidar_sight_kernel's
+// arithmetic into a byte mask in the carve's dist region (dead in this kernel; n * n bytes <= its 2 n * n floats), and
+// after the graph is written and a workgroup barrier the blocked pairs' receivers / senders are overwritten with the
+// pad node.  The graph writers are untouched.
+template <int ENGINE, int GOAL, int SD, int BLOCK, bool SIGHT = false>
 __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg, dgppo_lidar_observe_io io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Dims<0, -1, 0, 0> d(cfg);
@@ -3156,6 +3238,14 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
   const float* evec = lds + cv.evec;
   float* alpha = lds + cv.hpt;                                     // (n, R)
   uint64_t* keys = reinterpret_cast<uint64_t*>(lds + cv.alpha);    // (n, R)
+  uint8_t* unseen = reinterpret_cast<uint8_t*>(lds + cv.dist);     // (n, n), SIGHT only
+  if constexpr (SIGHT) {
+#pragma unroll 1
+    for (int q = tid; q < n * n; q += BLOCK) {
+      const int i = q / n, j = q - i * n;
+      unseen[q] = (i != j && pair_blocked(O, obst, evec, nxt, SD, i, j)) ? 1 : 0;
+    }
+  }
   const uint64_t seed = io.seed_ptr ? *io.seed_ptr : io.seed;
   const uint64_t stream = ((uint64_t)1 << 62) + 2 * (uint64_t)io.t;  // LidarNoise.STREAM_BASE + 2 t (+ 1: dropout)
   const int64_t e0 = (io.env_offset + env) * n * R;
@@ -3206,6 +3296,19 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
   }
   __syncthreads();
   graph_of_staged_hits<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
+  if constexpr (SIGHT) {
+    __syncthreads();  // the writers' index stores, by whichever thread, are behind this
+    int32_t* recv = io.receivers + env * io.edge_index_stride;
+    int32_t* send = io.senders + env * io.edge_index_stride;
+    const int pad = cfg.n_nodes - 1;
+#pragma unroll 1
+    for (int q = tid; q < n * n; q += BLOCK) {
+      if (unseen[q]) {
+        recv[q] = pad;
+        send[q] = pad;
+      }
+    }
+  }
 }
 
 // ---- reference env variants ------------------------------------------------------------------
@@ -4478,11 +4581,19 @@ extern "C" int dgppo_env_get_graph_hits(const dgppo_env_cfg* cfg, const dgppo_en
   return (int)hipGetLastError();
 }
 
-extern "C" int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream) {
+extern "C" int dgppo_lidar_sight(const dgppo_env_cfg* cfg, const dgppo_lidar_sight_io* io, void* stream) {
+  if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->obstacles || !io->visible) return DGPPO_EINVAL;
+  hipLaunchKernelGGL(lidar_sight_kernel, dim3((unsigned)io->n_env), dim3(64), 0, (hipStream_t)stream, *cfg, *io);
+  return (int)hipGetLastError();
+}
+
+// dgppo_lidar_observe and dgppo_lidar_observe_los: the same checks and launch, `allowed` the entry's flag bits
+static int lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream, int allowed) {
   if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
   if (cfg->variant != DGPPO_VARIANT_NONE) return DGPPO_EINVAL;  // LidarLine: the three launches (env.observe chains them)
-  if (io->t < 0 || io->env_offset < 0 || (io->flags & ~(DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT)))
-    return DGPPO_EINVAL;
+  if (io->t < 0 || io->env_offset < 0 || (io->flags & ~allowed)) return DGPPO_EINVAL;
   if (io->n_env == 0) return 0;
   if (!io->agent || !io->goal || !io->obstacles || !io->ray_dirs || !io->nodes || !io->edges || !io->out_states ||
       !io->receivers || !io->senders)
@@ -4492,11 +4603,24 @@ extern "C" int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_o
   if (shmem > 64 * 1024) return DGPPO_EINVAL;
   visit_engine_goal(*cfg, [&](auto e) {
     using E = decltype(e);
-    if constexpr (E::ENGINE != DGPPO_ENGINE_MPE)
-      hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128>), dim3((unsigned)io->n_env), dim3(128),
-                         shmem, (hipStream_t)stream, *cfg, *io);
+    if constexpr (E::ENGINE != DGPPO_ENGINE_MPE) {
+      if (io->flags & DGPPO_OBSERVE_SIGHT)
+        hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, true>), dim3((unsigned)io->n_env),
+                           dim3(128), shmem, (hipStream_t)stream, *cfg, *io);
+      else
+        hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128>), dim3((unsigned)io->n_env), dim3(128),
+                           shmem, (hipStream_t)stream, *cfg, *io);
+    }
   });
   return (int)hipGetLastError();
+}
+
+extern "C" int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream) {
+  return lidar_observe(cfg, io, stream, DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT);
+}
+
+extern "C" int dgppo_lidar_observe_los(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream) {
+  return lidar_observe(cfg, io, stream, DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT | DGPPO_OBSERVE_SIGHT);
 }
 
 // Rectangle.create (env/obstacle.py:39-56) on the host: the device make_rectangle's arithmetic, term for term

@@ -510,6 +510,23 @@ class MultiAgentEnv(ABC):
         torch.ops.dgppo.lidar_hits(self._cfg_handle, agent, alpha, self._ray_table(agent.device), hits)
         return hits
 
+    def line_of_sight(self, agent_states: torch.Tensor, obstacles) -> torch.Tensor:
+        """Which agents see each other past the obstacles (torch.ops.dgppo.lidar_sight): bool (B, n, n), entry
+        [b, i, j] False where an edge of some obstacle cuts the segment from agent i to agent j of env b, by the scan's
+        per-edge arithmetic (Rectangle.raytracing's alpha and beta both in [0, 1]).  The diagonal is True, coincident
+        agents see each other, agents do not occlude.  `utils.sensor.mask_unseen(graph, visible)` applies it to a
+        graph; `observe(..., occlusion=True)` does both in its one launch."""
+        what = "line_of_sight"
+        self._require_lidar(what)
+        agent = self._sensor_agents(what, agent_states)
+        B, n = int(agent.shape[0]), self._num_agents
+        ob = self._sensor_arg(what, "obstacles", getattr(obstacles, "packed", obstacles),
+                              (B, self.n_obs, self._obstacle_fields()), agent.device)
+        _lib.require_gpu(agent.device, "env.line_of_sight")
+        visible = torch.empty((B, n, n), dtype=torch.uint8, device=agent.device)
+        torch.ops.dgppo.lidar_sight(self._cfg_handle, agent, ob, visible)
+        return visible.view(torch.bool)
+
     def _get_graph_hits(self, state, out: Optional[GraphsTuple], lidar_data) -> GraphsTuple:
         what = "get_graph"
         self._require_lidar(what + ": lidar_data")
@@ -530,7 +547,7 @@ class MultiAgentEnv(ABC):
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
     def observe(self, state, t: int, *, sigma: float, dropout: float, seed, env_offset: int = 0,
-                out: Optional[GraphsTuple] = None) -> GraphsTuple:
+                out: Optional[GraphsTuple] = None, occlusion: bool = False) -> GraphsTuple:
         """The OBSERVED graph of the true `state` (get_graph's tuple, obstacles required) at step `t` under the
         range-noise / beam-dropout sensor model of utils/sensor.py, in one HIP launch (torch.ops.dgppo.lidar_observe):
         bit for bit `get_graph(state, lidar_data=lidar_hits(agent, LidarNoise(sigma, dropout, seed,
@@ -538,7 +555,11 @@ class MultiAgentEnv(ABC):
         the noise streams (ranks of a multi-GPU run pass rank * n_env).  seed: an int, or a 1-element int64 device
         tensor read at run time (replays of a captured rollout draw new noise).  sigma = dropout = 0 is the true
         graph.  `out` may be the graph whose env_states are `state`.  LidarLine runs the chained launches instead of
-        the fused kernel (same results)."""
+        the fused kernel (same results).
+
+        occlusion: obstacles also hide agents from each other -- every agent-agent edge whose receiver has no line of
+        sight to its sender goes to the pad node, `mask_unseen(observe(...), line_of_sight(agent, obstacle))` bit for
+        bit, in the same launch (torch.ops.dgppo.lidar_observe_los).  False takes exactly the path without it."""
         from ..utils.sensor import LidarNoise
 
         what = "observe"
@@ -562,13 +583,20 @@ class MultiAgentEnv(ABC):
         if g.states.dim() != 3 or g.states.shape[0] != B:
             raise ValueError(f"observe: out must hold {B} graphs")
         if self.cfg.variant != _lib.DGPPO_VARIANT_NONE:
-            return self._observe_chained(model, agent, goal, third, t, seed, env_offset, g)
+            if not occlusion:
+                return self._observe_chained(model, agent, goal, third, t, seed, env_offset, g)
+            from ..utils.sensor import mask_unseen
+
+            visible = self.line_of_sight(agent, third)  # before the graph is written: `out` may alias the state
+            return mask_unseen(self._observe_chained(model, agent, goal, third, t, seed, env_offset, g), visible)
         iseed = 0 if tkey is not None else int(seed) & 0xFFFFFFFFFFFFFFFF
         flags = (_lib.OBSERVE_NOISE if model.sigma > 0.0 else 0) | (_lib.OBSERVE_DROPOUT if model.dropout > 0.0 else 0)
-        torch.ops.dgppo.lidar_observe(self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
-                                      iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t,
-                                      model.sigma / sense_range, model._drop_below, flags, g.nodes, g.edges, g.states,
-                                      g.receivers, g.senders)
+        op = torch.ops.dgppo.lidar_observe
+        if occlusion:
+            op, flags = torch.ops.dgppo.lidar_observe_los, flags | _lib.OBSERVE_SIGHT
+        op(self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
+           iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t, model.sigma / sense_range, model._drop_below,
+           flags, g.nodes, g.edges, g.states, g.receivers, g.senders)
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
     def _observe_chained(self, model, agent, goal, third, t, seed, env_offset, g) -> GraphsTuple:

@@ -16,6 +16,8 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::lidar_hits     dgppo_lidar_hits     alphas -> top-k hit points, env/utils.py:66-79
   dgppo::env_get_graph_hits dgppo_env_get_graph_hits  get_graph(state, lidar_data), lidar_env/base.py:227-271
   dgppo::lidar_observe  dgppo_lidar_observe  scan, LidarNoise, hits and graph fused: the observed graph of a true state
+  dgppo::lidar_sight    dgppo_lidar_sight    which agents see each other past the obstacles (not in the reference)
+  dgppo::lidar_observe_los dgppo_lidar_observe_los  lidar_observe with the unseen agent-agent edges sent to the pad node
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
@@ -353,6 +355,15 @@ def lidar_observe(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_
     element ((env_offset + b) n + i) R + r under (seed or *key) and the streams of step t.  `key`: optional 1-element
     int64 device tensor read at run time (hipGraph replays)."""
     _lib.require_gpu(states.device, "dgppo::lidar_observe")
+    io = _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
+                     edges, states, receivers, senders)
+    _lib.check(_lib.load().dgppo_lidar_observe(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
+               "dgppo_lidar_observe")
+
+
+def _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
+                edges, states, receivers, senders) -> _lib.LidarObserveIO:
+    """The dgppo_lidar_observe_io of lidar_observe's / lidar_observe_los's arguments."""
     io = _lib.LidarObserveIO()
     io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
     io.goal, io.goal_stride = _p(goal), _stride(goal, 2)
@@ -372,13 +383,54 @@ def lidar_observe(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_
     else:
         io.seed, io.seed_ptr = int(seed) & 0xFFFFFFFFFFFFFFFF, None
     io.noise_scale, io.drop_below = float(noise_scale), float(drop_below)
-    _lib.check(_lib.load().dgppo_lidar_observe(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
-               "dgppo_lidar_observe")
+    return io
 
 
 @lidar_observe.register_fake
 def _lidar_observe_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
                         flags, nodes, edges, states, receivers, senders) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::lidar_observe_los", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
+def lidar_observe_los(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_dirs: Tensor,
+                      key: Optional[Tensor], seed: int, env_offset: int, t: int, noise_scale: float, drop_below: float,
+                      flags: int, nodes: Tensor, edges: Tensor, states: Tensor, receivers: Tensor,
+                      senders: Tensor) -> None:
+    """lidar_observe that also takes OBSERVE_SIGHT in `flags`: the observed graph with every agent-agent edge whose
+    receiver cannot see its sender past the obstacles (lidar_sight) routed to the pad node, in the same launch."""
+    _lib.require_gpu(states.device, "dgppo::lidar_observe_los")
+    io = _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
+                     edges, states, receivers, senders)
+    _lib.check(_lib.load().dgppo_lidar_observe_los(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
+               "dgppo_lidar_observe_los")
+
+
+@lidar_observe_los.register_fake
+def _lidar_observe_los_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
+                            flags, nodes, edges, states, receivers, senders) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::lidar_sight", mutates_args=("visible",))
+def lidar_sight(cfg: int, agent: Tensor, obstacles: Tensor, visible: Tensor) -> None:
+    """Line of sight between the agents of B envs: agent (B, n, sd) rows and obstacle records (B, O, 16) -> visible
+    (B, n, n) uint8, 1 where no obstacle edge cuts the segment from receiver i to sender j (the diagonal is 1).
+    Per-env strides are free; the trailing dims must be contiguous."""
+    _lib.require_gpu(visible.device, "dgppo::lidar_sight")
+    if visible.dtype != torch.uint8:
+        raise ValueError(f"dgppo::lidar_sight: visible must be uint8, got {visible.dtype}")
+    io = _lib.LidarSightIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.obstacles, io.obstacles_stride = _p(obstacles), _stride(obstacles, 2)
+    io.visible, io.visible_stride = visible.data_ptr(), _stride(visible, 2)
+    io.n_env = int(agent.shape[0])
+    _lib.check(_lib.load().dgppo_lidar_sight(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(visible)),
+               "dgppo_lidar_sight")
+
+
+@lidar_sight.register_fake
+def _lidar_sight_fake(cfg, agent, obstacles, visible) -> None:
     return None
 
 

@@ -24,6 +24,7 @@ from ..env.base import MultiAgentEnv
 from ..nn import kernels as K
 from ..nn.layers import GraphBatch
 from ..utils.graph import GraphsTuple
+from ..utils.sensor import mask_unseen
 from .data import Rollout
 
 
@@ -258,18 +259,23 @@ class SensorRolloutEngine(RolloutEngine):
     what they meant), and the observed graphs are `engine.observed`, batch shape (B, T).
 
     sensor: a callable (alpha (B, n, R), t) -> alpha_obs of the same shape, dtype and device (utils/sensor.py has
-    LidarNoise; `lambda a, t: a` reproduces the plain engine bit for bit).  MODE_DET or MODE_SAMPLE with an actor,
-    one lane, a Lidar env with obstacles; no hipGraph capture (a sensor is arbitrary Python)."""
+    LidarNoise; `lambda a, t: a` reproduces the plain engine bit for bit).  occlusion: obstacles also hide agents from
+    each other -- each observed graph then goes through utils.sensor.mask_unseen with env.line_of_sight of the true
+    state, and `sensor` may be None (the identity).  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env with
+    obstacles; no hipGraph capture (a sensor is arbitrary Python)."""
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
-                 actor=None, mode: int = RolloutEngine.MODE_DET, sensor=None, init_state=None):
+                 actor=None, mode: int = RolloutEngine.MODE_DET, sensor=None, init_state=None,
+                 occlusion: bool = False):
+        if sensor is None and occlusion:
+            sensor = lambda alpha, t: alpha  # noqa: E731
         if not callable(sensor):
             raise ValueError("SensorRolloutEngine: sensor must be a callable (alpha, t) -> alpha_obs")
         if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
             raise ValueError("SensorRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
         env._require_lidar("SensorRolloutEngine")
         super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
-        self.sensor = sensor
+        self.sensor, self.occlusion = sensor, bool(occlusion)
         self.obs_buf = env.empty_graph((self.T, self.B), self.device)  # time-major, like buf
 
     def _observed_at(self, t: int) -> GraphsTuple:
@@ -291,8 +297,10 @@ class SensorRolloutEngine(RolloutEngine):
             agent = self.buf.states[t][:, :n]
             goal = self.buf.states[t][:, n:n + env.num_goals]
             alpha_obs = self.sensor(env.lidar_scan(agent, self.obstacles), t)
-            env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
-                          lidar_data=env.lidar_hits(agent, alpha_obs))
+            seen = env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
+                                 lidar_data=env.lidar_hits(agent, alpha_obs))
+            if self.occlusion:
+                mask_unseen(seen, env.line_of_sight(agent, self.obstacles))
             self._act(t)
             cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
 
@@ -319,7 +327,8 @@ class NoisyLidarRolloutEngine(RolloutEngine):
     observed from the final true state (the update's final-value graph).  The noise seed is the engine's key tensor --
     a replay with a new key draws new noise -- under the sensor's stream ids (2^62 + 2t, + 1), which cannot collide
     with the policy's (env_offset << 32) | t while env_offset < 2^30 (check_env_offset refuses more); env b's beams
-    draw at row env_offset + b.
+    draw at row env_offset + b.  occlusion: env.observe(..., occlusion=True), the agents hidden from each other by
+    obstacles dropped from every observed graph in the same launch.
 
     `run` returns the true Rollout; `observed_rollout()` the Rollout the algorithms train on: graph and next_graph
     the observed ones, every other field the true run's.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env
@@ -327,14 +336,14 @@ class NoisyLidarRolloutEngine(RolloutEngine):
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_SAMPLE, sigma: float = 0.0, dropout: float = 0.0,
-                 init_state=None):
+                 init_state=None, occlusion: bool = False):
         from ..utils.sensor import LidarNoise
 
         if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
             raise ValueError("NoisyLidarRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
         env._require_lidar("NoisyLidarRolloutEngine")
         model = LidarNoise(sigma, dropout, 0, sense_range=float(env.params["comm_radius"]))  # checks both
-        self.sigma, self.dropout = model.sigma, model.dropout
+        self.sigma, self.dropout, self.occlusion = model.sigma, model.dropout, bool(occlusion)
         super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
         self.obs = env.empty_graph((self.T + 1, self.B), self.device)  # time-major, like buf
 
@@ -350,7 +359,7 @@ class NoisyLidarRolloutEngine(RolloutEngine):
         env, n = self.env, self.env.num_agents
         s = self.buf.states[t]
         env.observe((s[:, :n], s[:, n:n + env.num_goals], self.obstacles), t, sigma=self.sigma, dropout=self.dropout,
-                    seed=self.key, env_offset=self.env_offset, out=self._observed_at(t))
+                    seed=self.key, env_offset=self.env_offset, out=self._observed_at(t), occlusion=self.occlusion)
 
     def _run(self):
         env = self.env

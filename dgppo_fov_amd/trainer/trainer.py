@@ -68,10 +68,13 @@ class Trainer:
         assert self.n_env_test <= 1_000, "n_env_test must be less than or equal to 1_000"
         if self._test_engine is None:
             sensor = getattr(self.algo, "sensor", None)
-            if sensor is not None:  # trained under a sensor model: the true costs under sensed control
+            occlusion = bool(getattr(self.algo, "occlusion", False))
+            if sensor is not None or occlusion:  # trained under a sensor model: the true costs under sensed control
+                sigma, dropout = sensor or (0.0, 0.0)
                 self._test_engine = NoisyLidarRolloutEngine(
                     self.env_test, self.n_env_test, self.env_test.max_episode_steps, self.algo.device,
-                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sigma=sensor[0], dropout=sensor[1])
+                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sigma=sigma, dropout=dropout,
+                    occlusion=occlusion)
             else:
                 self._test_engine = RolloutEngine(self.env_test, self.n_env_test, self.env_test.max_episode_steps,
                                                   self.algo.device, actor=self.algo.actor, mode=RolloutEngine.MODE_DET)

@@ -4,6 +4,9 @@ The scan is `alpha` (B, n, R): per beam the hit distance as a fraction of the se
 comm_radius), NO_RETURN = 1e6 where nothing is hit (the reference's env/utils.py:115-130).  A sensor is any callable
 `sensor(alpha, t) -> alpha_obs` of the same shape and device; trainer/rollout.py SensorRolloutEngine runs one in the
 loop, `env.get_graph(state, lidar_data=env.lidar_hits(agent, alpha_obs))` builds a graph from its output.
+
+The other half of an observed graph, who sees whom: `mask_unseen(graph, env.line_of_sight(agent, obstacles))` drops the
+agent-agent edges that an obstacle cuts (`env.observe(..., occlusion=True)` is the fused form).
 """
 from __future__ import annotations
 
@@ -26,6 +29,26 @@ def ranges_to_alpha(ranges: torch.Tensor, sense_range: float) -> torch.Tensor:
     r = ranges.to(torch.float32)
     ok = torch.isfinite(r) & (r >= 0) & (r <= sense_range)
     return torch.where(ok, r / sense_range, torch.full_like(r, NO_RETURN))
+
+
+def mask_unseen(graph, visible: torch.Tensor):
+    """Hide the neighbours a receiver cannot see: for every pair with `~visible[..., i, j]` (bool, the graph's batch
+    shape + (n, n), `env.line_of_sight`), edge i * n + j of the leading agent-agent block gets receivers = senders =
+    the pad node (the last node), as out-of-range pairs are stored.  In place on the graph's index tensors; edge
+    features, nodes, states and all other edges are untouched.  Returns the graph."""
+    if not isinstance(visible, torch.Tensor) or visible.dtype != torch.bool:
+        raise ValueError("mask_unseen: visible must be a bool tensor")
+    recv, send = graph.receivers, graph.senders
+    if visible.dim() < 2 or visible.shape[-1] != visible.shape[-2] or tuple(visible.shape[:-2]) != tuple(recv.shape[:-1]):
+        raise ValueError(f"mask_unseen: visible must be {tuple(recv.shape[:-1])} + (n, n), got {tuple(visible.shape)}")
+    n = int(visible.shape[-1])
+    if n * n > recv.shape[-1] or visible.device != recv.device:
+        raise ValueError("mask_unseen: visible does not fit the graph's agent-agent edges or is on another device")
+    pad = int(graph.states.shape[-2]) - 1
+    hide = ~visible.reshape(tuple(visible.shape[:-2]) + (n * n,))
+    recv[..., :n * n].masked_fill_(hide, pad)
+    send[..., :n * n].masked_fill_(hide, pad)
+    return graph
 
 
 class LidarNoise:

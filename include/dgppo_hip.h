@@ -302,6 +302,34 @@ typedef struct dgppo_lidar_observe_io {
 
 int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream);
 
+/* Line-of-sight neighbour sensing: obstacles hide agents from each other.  For an ordered pair (receiver i, sender
+ * j), i != j, with P / Q = columns 0, 1 of agent rows i / j: blocked[i, j] = some edge of some obstacle is `valid`
+ * (alpha and beta both in [0, 1]) by Rectangle.raytracing's per-edge expressions (dgppo/env/obstacle.py:74-105) with
+ * the ray from P to Q, in fp32 and the reference's operation order.  NaN and det == 0 make that EDGE invalid, so
+ * coincident agents see each other and a segment parallel to two sides of a rectangle it crosses is blocked by the
+ * other two; the scan's is_in factor is not applied; each direction is computed on its own; agents do not occlude.
+ * visible = !blocked, the diagonal 1.
+ *
+ * dgppo_lidar_sight: `agent` (n, sd) rows, `obstacles` (O, 16) records -> `visible` (n, n) bytes (0 / 1), per-env
+ * strides in elements; one launch, any n the cfg allows.  The Lidar engines with n_obs > 0, LidarLine included; the
+ * MPE and VMAS engines, n_obs == 0 and a NULL pointer return DGPPO_EINVAL without a launch; n_env == 0 returns 0.
+ *
+ * dgppo_lidar_observe_los: dgppo_lidar_observe that also accepts DGPPO_OBSERVE_SIGHT in `flags`: the same graph,
+ * with receivers[e] = senders[e] = the pad node (n_nodes - 1) for every agent-agent edge e = i n + j whose pair is
+ * not visible.  Edge features, nodes, states and all other edges are those of dgppo_lidar_observe; without the flag
+ * the two entries are the same launch.  Same refusals (LidarLine: env.observe masks the chained graph).  No ABI
+ * number change (new symbols only). */
+#define DGPPO_OBSERVE_SIGHT 4
+typedef struct dgppo_lidar_sight_io {
+  const float* agent;       int64_t agent_stride;
+  const float* obstacles;   int64_t obstacles_stride;
+  uint8_t* visible;         int64_t visible_stride;
+  int32_t n_env;
+} dgppo_lidar_sight_io;
+
+int dgppo_lidar_sight(const dgppo_env_cfg* cfg, const dgppo_lidar_sight_io* io, void* stream);
+int dgppo_lidar_observe_los(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream);
+
 /* Host-side helper: `count` obstacle records (count x 16, DGPPO_OBST_FIELDS layout) from HOST arrays center
  * (count x 2), width, height, theta (count each) = Rectangle.create (dgppo/env/obstacle.py:39-56) with the fp32
  * sin / cos and operation order of the reset kernels, so a scene can be assembled without a GPU. */

@@ -30,7 +30,9 @@ Beyond the reference: `--scene PATH` evaluates on the initial states stored in a
 policy (trainer/rollout.py SensorRolloutEngine, utils/sensor.py LidarNoise seeded from --seed): the policy sees LiDAR
 ranges with Gaussian noise of std SIGMA world units and beams dropped with probability P, while the env steps, the
 rewards and the costs stay the true ones.  Either flag routes the evaluation through that loop; the summary line then
-names both values."""
+names both values.  `--lidar-occlusion` (same envs, with or without the noise flags, no config.yaml entry needed) also
+drops every agent-agent edge whose receiver has no line of sight to its sender past the obstacles from the graphs the
+policy sees (env.line_of_sight, utils/sensor.py mask_unseen)."""
 import argparse
 import os
 
@@ -68,12 +70,12 @@ def test(args):
                      max_grad_norm=2.0, seed=cfg["seed"], use_rnn=cfg.get("use_rnn", True),
                      rnn_layers=cfg.get("rnn_layers", 1), use_lstm=cfg.get("use_lstm", False),
                      batch_size=cfg.get("batch_size", 16384), rnn_step=cfg.get("rnn_step", 16), device=dev)
-    sensed = args.lidar_noise is not None or args.lidar_dropout is not None
+    sensed = args.lidar_noise is not None or args.lidar_dropout is not None or args.lidar_occlusion
     if sensed:  # refused before anything is loaded or run
         sigma, drop = args.lidar_noise or 0.0, args.lidar_dropout or 0.0
         if env._obstacle_fields() == 0 or env.n_obs == 0 or not hasattr(env, "lidar_scan"):
-            raise SystemExit(f"--lidar-noise / --lidar-dropout need a LiDAR env with obstacles; {type(env).__name__} "
-                             f"with {env.n_obs} obstacles has no LiDAR")
+            raise SystemExit("--lidar-noise / --lidar-dropout / --lidar-occlusion need a LiDAR env with obstacles; "
+                             f"{type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
         if not sigma >= 0.0 or not 0.0 <= drop <= 1.0:
             raise SystemExit(f"--lidar-noise must be >= 0 and --lidar-dropout in [0, 1], got {sigma} and {drop}")
     if args.cbf is not None and args.video and not args.no_video:  # refused before anything is loaded or run
@@ -114,7 +116,8 @@ def test(args):
 
         sensor = LidarNoise(sigma, drop, args.seed, sense_range=float(env.params["comm_radius"]))
         eng = SensorRolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset,
-                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state)
+                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state,
+                                  occlusion=args.lidar_occlusion)
     else:
         eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
                             mode=mode, init_state=init_state)
@@ -133,7 +136,8 @@ def test(args):
     safe_mean, safe_std = (1 - is_unsafe).mean(), (1 - is_unsafe).std()
     print(f"reward: {np.mean(rewards):.3f}, min/max reward: {np.min(rewards):.3f}/{np.max(rewards):.3f}, "
           f"cost: {np.mean(costs):.3f}, min/max cost: {np.min(costs):.3f}/{np.max(costs):.3f}, "
-          f"safe_rate: {safe_mean * 100:.3f}%" + (f", lidar noise: {sigma:g}, lidar dropout: {drop:g}" if sensed else ""))
+          f"safe_rate: {safe_mean * 100:.3f}%" + (f", lidar noise: {sigma:g}, lidar dropout: {drop:g}" if sensed else "") +
+          (", lidar occlusion: on" if args.lidar_occlusion else ""))
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(f"{env.num_agents},{args.epi},{env.max_episode_steps},{env.area_size},{env.params['n_obs']},"
@@ -187,6 +191,7 @@ def build_parser():
     # sensor in the loop (Lidar envs): range noise std in world units, per-beam dropout probability
     parser.add_argument("--lidar-noise", type=float, default=None, metavar="SIGMA")
     parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P")
+    parser.add_argument("--lidar-occlusion", action="store_true", default=False)  # obstacles hide agents from each other
     return parser
 
 

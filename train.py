@@ -8,7 +8,9 @@ Beyond the reference: `--lidar-noise SIGMA` / `--lidar-dropout P` (Lidar envs wi
 informarl_lagr) train under the sensor model `test.py` evaluates with (utils/sensor.py LidarNoise, one fused kernel
 launch per step inside the captured rollout): the actor, Vl and Vh all see LiDAR ranges with Gaussian noise of std SIGMA
 world units and beams dropped with probability P, while the env steps, the rewards and the costs stay the true ones.
-The noise is seeded by each rollout's key, so a resumed run continues the same sequence."""
+The noise is seeded by each rollout's key, so a resumed run continues the same sequence.  `--lidar-occlusion` (same envs
+and algorithms, with or without the noise flags) also lets obstacles hide agents from each other: an agent-agent edge
+whose receiver has no line of sight to its sender is dropped from every graph the networks see."""
 import argparse
 import datetime
 import json
@@ -35,6 +37,8 @@ def check_resume_args(args, log_dir, world=None):
     cur = dict(vars(args))
     cur["_world_size"] = int(os.environ.get("WORLD_SIZE", "1")) if world is None else int(world)
     saved.setdefault("_world_size", 1)  # runs saved before the world size was recorded ran on one GPU
+    if cur.get("lidar_occlusion"):
+        saved.setdefault("lidar_occlusion", False)  # runs saved before the flag existed trained without it
     diff = {k: (saved[k], cur.get(k)) for k in saved if k not in RESUME_FREE and saved[k] != cur.get(k)}
     if diff:
         raise SystemExit("--resume: flags differ from the run's own (saved, given): " +
@@ -82,7 +86,7 @@ def train(args):
         coef_ent=args.coef_ent, rnn_step=args.rnn_step, gamma=0.99, clip_eps=args.clip_eps,
         lagr_init=args.lagr_init, lr_lagr=args.lr_lagr, train_steps=args.steps,
         cbf_schedule=not args.no_cbf_schedule, cost_schedule=args.cost_schedule, device=device,
-        lidar_noise=args.lidar_noise, lidar_dropout=args.lidar_dropout)
+        lidar_noise=args.lidar_noise, lidar_dropout=args.lidar_dropout, lidar_occlusion=args.lidar_occlusion)
     if args.load_checkpoint:
         print(f"> Loading checkpoint from {args.load_checkpoint}, step {args.load_step}")
         algo.load(args.load_checkpoint, args.load_step)
@@ -174,6 +178,8 @@ def build_parser():
     parser.add_argument("--lidar-noise", type=float, default=None, metavar="SIGMA",
                         help="range noise std in world units: actor, Vl and Vh train on the observed graphs")
     parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P", help="per-beam dropout probability")
+    parser.add_argument("--lidar-occlusion", action="store_true", default=False,
+                        help="obstacles hide agents from each other in the graphs the networks see")
     return parser
 
 
