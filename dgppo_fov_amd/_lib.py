@@ -173,7 +173,8 @@ class EnvGraphHitsIO(ctypes.Structure):  # dgppo_env_graph_hits_io
 
 
 OBSERVE_NOISE, OBSERVE_DROPOUT = 1, 2  # include/dgppo_hip.h DGPPO_OBSERVE_*
-OBSERVE_SIGHT = 4  # dgppo_lidar_observe_los only
+OBSERVE_SIGHT = 4  # dgppo_lidar_observe_los and dgppo_lidar_observe_fov
+OBSERVE_FOV = 8  # dgppo_lidar_observe_fov only
 
 
 class LidarObserveIO(ctypes.Structure):  # dgppo_lidar_observe_io
@@ -198,6 +199,15 @@ class LidarSightIO(ctypes.Structure):  # dgppo_lidar_sight_io
         ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
         ("obstacles", c_f32p), ("obstacles_stride", ctypes.c_int64),
         ("visible", c_f32p), ("visible_stride", ctypes.c_int64),
+        ("n_env", ctypes.c_int32),
+    ]
+
+
+class AgentFovIO(ctypes.Structure):  # dgppo_agent_fov_io
+    _fields_ = [
+        ("agent", c_f32p), ("agent_stride", ctypes.c_int64),
+        ("in_fov", c_f32p), ("in_fov_stride", ctypes.c_int64),
+        ("half_angle_deg", ctypes.c_float),
         ("n_env", ctypes.c_int32),
     ]
 
@@ -441,6 +451,9 @@ SIGNATURES = {
     "dgppo_lidar_sight": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarSightIO), ctypes.c_void_p]),
     "dgppo_lidar_observe_los": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO),
                                                ctypes.c_void_p]),
+    "dgppo_agent_fov": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(AgentFovIO), ctypes.c_void_p]),
+    "dgppo_lidar_observe_fov": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO),
+                                               ctypes.c_float, ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),

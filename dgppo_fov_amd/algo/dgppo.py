@@ -138,7 +138,8 @@ class DGPPO:
                  rnn_layers: int = 1, rnn_step: int = 16, use_lstm: bool = False, alpha: float = 10.0,
                  cbf_eps: float = 1e-2, cbf_weight: float = 1.0, train_steps: int = int(1e5),
                  cbf_schedule: bool = True, device=None, lidar_noise: Optional[float] = None,
-                 lidar_dropout: Optional[float] = None, lidar_occlusion: bool = False, **kwargs):
+                 lidar_dropout: Optional[float] = None, lidar_occlusion: bool = False,
+                 lidar_fov: Optional[float] = None, **kwargs):
         if rnn_layers < 1:
             raise ValueError(f"rnn_layers {rnn_layers} < 1")
         self._env = env
@@ -150,6 +151,11 @@ class DGPPO:
         self.occlusion = bool(lidar_occlusion)
         if self.occlusion and self.sensor is None:
             self._sensor_model(env, 0.0, 0.0)  # the same refusals as the noise flags
+        # lidar_fov: a half angle in degrees -- the senders outside the receiver's camera cone are hidden as well
+        # (env.observe(fov=deg), the envs with a heading); on its own it selects the same engine.  None and 180: no cone
+        if lidar_fov is not None and self.sensor is None:
+            self._sensor_model(env, 0.0, 0.0)
+        self.fov = env._fov_angle("lidar_fov", lidar_fov)
         self.device = torch.device(device) if device is not None else env.device
         self._node_dim, self._edge_dim, self._action_dim, self._n_agents = node_dim, edge_dim, action_dim, n_agents
         self.actor_gnn_layers, self.Vl_gnn_layers, self.Vh_gnn_layers = actor_gnn_layers, Vl_gnn_layers, Vh_gnn_layers
@@ -210,10 +216,10 @@ class DGPPO:
 
         if not cls.SENSOR_OK:
             raise ValueError(f"{cls.__name__} evaluates env.get_cost on the rollout's graphs, which must be the true "
-                             "ones: lidar_noise / lidar_dropout / lidar_occlusion are not supported (dgppo, informarl, "
-                             "informarl_lagr are)")
+                             "ones: lidar_noise / lidar_dropout / lidar_occlusion / lidar_fov are not supported (dgppo, "
+                             "informarl, informarl_lagr are)")
         if env.ENGINE in env._VMAS_ENGINES or env._obstacle_fields() == 0 or env.n_obs == 0:
-            raise ValueError("lidar_noise / lidar_dropout / lidar_occlusion need a LiDAR env with obstacles; "
+            raise ValueError("lidar_noise / lidar_dropout / lidar_occlusion / lidar_fov need a LiDAR env with obstacles; "
                              f"{type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
         model = LidarNoise(lidar_noise or 0.0, lidar_dropout or 0.0, 0, sense_range=float(env.params["comm_radius"]))
         return model.sigma, model.dropout
@@ -315,8 +321,9 @@ class DGPPO:
 
     @property
     def sensed(self) -> bool:
-        """Whether collect and det_rollout return observed graphs (a sensor model, occlusion, or both)."""
-        return self.sensor is not None or self.occlusion
+        """Whether collect and det_rollout return observed graphs (a sensor model, occlusion, a field of view, or any
+        of them together)."""
+        return self.sensor is not None or self.occlusion or self.fov is not None
 
     def _rollout_lanes(self, n_env: int) -> int:
         """Env slices on separate streams (RolloutEngine lanes): DGPPO_ROLLOUT_LANES when the slices are
@@ -331,7 +338,8 @@ class DGPPO:
                 sigma, dropout = self.sensor or (0.0, 0.0)
                 eng = NoisyLidarRolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                               env_offset=self.rank * n_env, actor=self.actor, mode=mode,
-                                              sigma=sigma, dropout=dropout, occlusion=self.occlusion)
+                                              sigma=sigma, dropout=dropout, occlusion=self.occlusion,
+                                              fov=self.fov)
             else:
                 eng = RolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                     env_offset=self.rank * n_env, actor=self.actor, mode=mode,

@@ -3203,6 +3203,38 @@ __global__ __launch_bounds__(64) void lidar_sight_kernel(dgppo_env_cfg cfg, dgpp
   }
 }
 
+// ---- field of view between agents ------------------------------------------------------------------
+// Is agent j inside agent i's forward cone (rows of `rows`, row stride rs: x, y, heading cos, heading sin)?  The FoV
+// cost's arithmetic and operation order (cq[2] of the step kernels, get_cost_omni's h_a), cb the cone's cosine: the
+// heading as given, NaN unseen (the comparison fails), coincident agents (nrm = lx = 0) seen exactly when cb <= 0.
+__device__ __forceinline__ bool pair_in_fov(const float* rows, int rs, int i, int j, float cb) {
+  const float xi0 = rows[i * rs + 0], xi1 = rows[i * rs + 1], xi2 = rows[i * rs + 2], xi3 = rows[i * rs + 3];
+  const float dx = rows[j * rs + 0] - xi0, dy = rows[j * rs + 1] - xi1;
+  const float lx = xi2 * dx + xi3 * dy;
+  const float ly = (-xi3) * dx + xi2 * dy;
+  const float nrm = norm2(lx, ly);
+  return (cb * (nrm + 1e-8f) - lx) <= 0.0f;
+}
+
+// dgppo_agent_fov: one wave per env, lanes striding over the n * n ordered (receiver, sender) pairs as in
+// lidar_sight_kernel; the first four columns of the agent rows staged in LDS.  in_fov[i, j] = pair_in_fov, the
+// diagonal 1 without a test.  cb comes from the host (fov_cos, dgppo_env_cfg_finalize's routine).
+__global__ __launch_bounds__(64) void agent_fov_kernel(dgppo_env_cfg cfg, dgppo_agent_fov_io io, float cb) {
+  __shared__ __attribute__((aligned(16))) float rows[4 * kMaxAgents];
+  const int n = cfg.n_agents, sd = cfg.state_dim;
+  const int lane = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  const float* ag = io.agent + env * io.agent_stride;
+  for (int idx = lane; idx < 4 * n; idx += 64) rows[idx] = ag[(idx >> 2) * sd + (idx & 3)];
+  __syncthreads();
+  uint8_t* out = io.in_fov + env * io.in_fov_stride;
+#pragma unroll 1
+  for (int q = lane; q < n * n; q += 64) {
+    const int i = q / n, j = q - i * n;
+    out[q] = (i == j || pair_in_fov(rows, 4, i, j, cb)) ? 1 : 0;
+  }
+}
+
 // dgppo_lidar_observe: scan | LidarNoise | hits | graph in one launch, one workgroup per env.  The beams of all agents
 // are cast by lidar_alpha_kernel's arithmetic into LDS (the alphas in the carve's hpt region, their sort keys in its
 // alpha region), the sensor model (utils/sensor.py LidarNoise.__call__, op for op) edits each alpha as it is made,
@@ -3212,7 +3244,11 @@ __global__ __launch_bounds__(64) void lidar_sight_kernel(dgppo_env_cfg cfg, dgpp
 // arithmetic into a byte mask in the carve's dist region (dead in this kernel; n * n bytes <= its 2 n * n floats), and
 // after the graph is written and a workgroup barrier the blocked pairs' receivers / senders are overwritten with the
 // pad node.  The graph writers are untouched.
-template <int ENGINE, int GOAL, int SD, int BLOCK, bool SIGHT = false>
+// FOV (dgppo_lidar_observe_fov with DGPPO_OBSERVE_FOV; the engines with a heading only): pair_in_fov on the agent rows
+// staged in nxt ORs "outside the receiver's cone" into the same byte mask, for the same post-pass.  The cone's cosine
+// arrives as cfg.c_cos_fov: the entry launches with a copy of the cfg that holds the sensed cone there (this kernel
+// evaluates no cost, so nothing else reads the field), which leaves the kernel's arguments as they were.
+template <int ENGINE, int GOAL, int SD, int BLOCK, bool SIGHT = false, bool FOV = false>
 __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg, dgppo_lidar_observe_io io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Dims<0, -1, 0, 0> d(cfg);
@@ -3238,12 +3274,18 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
   const float* evec = lds + cv.evec;
   float* alpha = lds + cv.hpt;                                     // (n, R)
   uint64_t* keys = reinterpret_cast<uint64_t*>(lds + cv.alpha);    // (n, R)
-  uint8_t* unseen = reinterpret_cast<uint8_t*>(lds + cv.dist);     // (n, n), SIGHT only
-  if constexpr (SIGHT) {
+  uint8_t* unseen = reinterpret_cast<uint8_t*>(lds + cv.dist);     // (n, n), SIGHT / FOV only
+  if constexpr (SIGHT || FOV) {
+    static_assert(!FOV || ENGINE == DGPPO_ENGINE_BICYCLE || ENGINE == DGPPO_ENGINE_OMNI, "FOV needs a heading");
 #pragma unroll 1
     for (int q = tid; q < n * n; q += BLOCK) {
       const int i = q / n, j = q - i * n;
-      unseen[q] = (i != j && pair_blocked(O, obst, evec, nxt, SD, i, j)) ? 1 : 0;
+      bool hide = false;
+      if (i != j) {
+        if constexpr (SIGHT) hide = pair_blocked(O, obst, evec, nxt, SD, i, j);
+        if constexpr (FOV) hide = hide | !pair_in_fov(nxt, SD, i, j, cfg.c_cos_fov);
+      }
+      unseen[q] = hide ? 1 : 0;
     }
   }
   const uint64_t seed = io.seed_ptr ? *io.seed_ptr : io.seed;
@@ -3296,7 +3338,7 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
   }
   __syncthreads();
   graph_of_staged_hits<ENGINE, GOAL, SD, BLOCK>(cfg, io, d, cv, lds, env);
-  if constexpr (SIGHT) {
+  if constexpr (SIGHT || FOV) {
     __syncthreads();  // the writers' index stores, by whichever thread, are behind this
     int32_t* recv = io.receivers + env * io.edge_index_stride;
     int32_t* send = io.senders + env * io.edge_index_stride;
@@ -4589,11 +4631,44 @@ extern "C" int dgppo_lidar_sight(const dgppo_env_cfg* cfg, const dgppo_lidar_sig
   return (int)hipGetLastError();
 }
 
-// dgppo_lidar_observe and dgppo_lidar_observe_los: the same checks and launch, `allowed` the entry's flag bits
-static int lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream, int allowed) {
+// The cone's cosine of a half angle in degrees, 0 < deg <= 180 (else, NaN included, false): dgppo_env_cfg_finalize's
+// expression for c_cos_fov, so the cone that is sensed at deg == fov_angle_deg is the cone that is constrained.
+static bool fov_cos(float deg, float* cb) {
+  if (!(deg > 0.0f && deg <= 180.0f)) return false;
+  float sb;
+  sincos32(deg * (float)(M_PI / 180.0), &sb, cb);
+  return true;
+}
+
+static bool has_heading(const dgppo_env_cfg* cfg) {
+  return cfg->engine == DGPPO_ENGINE_BICYCLE || cfg->engine == DGPPO_ENGINE_OMNI;
+}
+
+extern "C" int dgppo_agent_fov(const dgppo_env_cfg* cfg, const dgppo_agent_fov_io* io, void* stream) {
+  if (validate(cfg) || vmas::is_vmas(cfg) || !has_heading(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
+  float cb;
+  if (!fov_cos(io->half_angle_deg, &cb)) return DGPPO_EINVAL;
+  if (io->n_env == 0) return 0;
+  if (!io->agent || !io->in_fov) return DGPPO_EINVAL;
+  hipLaunchKernelGGL(agent_fov_kernel, dim3((unsigned)io->n_env), dim3(64), 0, (hipStream_t)stream, *cfg, *io, cb);
+  return (int)hipGetLastError();
+}
+
+// dgppo_lidar_observe, dgppo_lidar_observe_los and dgppo_lidar_observe_fov: the same checks and launch, `allowed` the
+// entry's flag bits, `deg` the cone's half angle (read with DGPPO_OBSERVE_FOV only)
+static int lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream, int allowed,
+                         float deg = 180.0f) {
   if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
   if (cfg->variant != DGPPO_VARIANT_NONE) return DGPPO_EINVAL;  // LidarLine: the three launches (env.observe chains them)
   if (io->t < 0 || io->env_offset < 0 || (io->flags & ~allowed)) return DGPPO_EINVAL;
+  dgppo_env_cfg seen = *cfg;  // the FOV kernels read the sensed cone's cosine from their cfg's c_cos_fov
+  bool fov = false;
+  if (io->flags & DGPPO_OBSERVE_FOV) {
+    // the fused form is built for the two envs with a heading (both GOAL_TARGET); dgppo_agent_fov serves any goal mode
+    if (!has_heading(cfg) || cfg->goal_mode != DGPPO_GOAL_TARGET || !fov_cos(deg, &seen.c_cos_fov))
+      return DGPPO_EINVAL;
+    fov = deg != 180.0f;  // exactly 180: no cone, the launch of the other bits
+  }
   if (io->n_env == 0) return 0;
   if (!io->agent || !io->goal || !io->obstacles || !io->ray_dirs || !io->nodes || !io->edges || !io->out_states ||
       !io->receivers || !io->senders)
@@ -4603,6 +4678,18 @@ static int lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io*
   if (shmem > 64 * 1024) return DGPPO_EINVAL;
   visit_engine_goal(*cfg, [&](auto e) {
     using E = decltype(e);
+    if constexpr ((E::ENGINE == DGPPO_ENGINE_BICYCLE || E::ENGINE == DGPPO_ENGINE_OMNI) &&
+                  E::GOAL == DGPPO_GOAL_TARGET) {  // LidarBicycleTarget, LidarOmniTarget: four kernels
+      if (fov) {
+        if (io->flags & DGPPO_OBSERVE_SIGHT)
+          hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, true, true>),
+                             dim3((unsigned)io->n_env), dim3(128), shmem, (hipStream_t)stream, seen, *io);
+        else
+          hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, false, true>),
+                             dim3((unsigned)io->n_env), dim3(128), shmem, (hipStream_t)stream, seen, *io);
+        return;
+      }
+    }
     if constexpr (E::ENGINE != DGPPO_ENGINE_MPE) {
       if (io->flags & DGPPO_OBSERVE_SIGHT)
         hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, true>), dim3((unsigned)io->n_env),
@@ -4621,6 +4708,13 @@ extern "C" int dgppo_lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_o
 
 extern "C" int dgppo_lidar_observe_los(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream) {
   return lidar_observe(cfg, io, stream, DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT | DGPPO_OBSERVE_SIGHT);
+}
+
+extern "C" int dgppo_lidar_observe_fov(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io,
+                                       float half_angle_deg, void* stream) {
+  return lidar_observe(cfg, io, stream,
+                       DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT | DGPPO_OBSERVE_SIGHT | DGPPO_OBSERVE_FOV,
+                       half_angle_deg);
 }
 
 // Rectangle.create (env/obstacle.py:39-56) on the host: the device make_rectangle's arithmetic, term for term

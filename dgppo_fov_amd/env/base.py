@@ -527,6 +527,42 @@ class MultiAgentEnv(ABC):
         torch.ops.dgppo.lidar_sight(self._cfg_handle, agent, ob, visible)
         return visible.view(torch.bool)
 
+    _HEADING_ENGINES = (_lib.DGPPO_ENGINE_BICYCLE, _lib.DGPPO_ENGINE_OMNI)
+
+    def _fov_angle(self, what: str, fov) -> Optional[float]:
+        """The half angle of a sensing cone in degrees, or None for no cone (`fov` None or exactly 180).  A cone needs
+        an env whose state carries a heading (LidarBicycleTarget, LidarOmniTarget) and 0 < fov <= 180: ValueError
+        otherwise (NotImplementedError for the VMAS envs), before the GPU is touched."""
+        if fov is None:
+            return None
+        if self.ENGINE in self._VMAS_ENGINES:
+            raise NotImplementedError(f"{what}: the VMAS envs have no field-of-view sensor model")
+        if self.ENGINE not in self._HEADING_ENGINES:
+            raise ValueError(f"{what}: a field of view needs a heading in the state (LidarBicycleTarget, "
+                             f"LidarOmniTarget); {type(self).__name__} has no heading")
+        deg = float(fov)
+        if not 0.0 < deg <= 180.0:
+            raise ValueError(f"{what}: the half angle must be in (0, 180] degrees, got {fov}")
+        return None if deg == 180.0 else deg
+
+    def field_of_view(self, agent_states: torch.Tensor, half_angle_deg: float) -> torch.Tensor:
+        """Which agents lie in each other's camera cone (torch.ops.dgppo.agent_fov): bool (B, n, n), entry [b, i, j]
+        True where agent j of env b is inside the forward cone of half angle `half_angle_deg` (0 < deg <= 180) around
+        agent i's heading (columns 2, 3 of its row, used as given), by the FoV cost's own fp32 arithmetic: at
+        `params["fov_angle_deg"]`, `[b, i, i + 1] == (cost[b, i, 2] < 0)` of LidarOmniTarget bit for bit.  The diagonal
+        is True, a NaN row sees no one and is seen by no one, coincident agents see each other exactly when the cone's
+        cosine is <= 0 (the formula's quirk), and there is no range test.  Only the envs with a heading; no obstacles
+        are needed.  `utils.sensor.mask_unseen(graph, in_fov)` applies it to a graph; `observe(..., fov=deg)` does both
+        in its one launch."""
+        what = "field_of_view"
+        self._fov_angle(what, float("nan") if half_angle_deg is None else half_angle_deg)  # the env, then the domain
+        agent = self._sensor_agents(what, agent_states)
+        B, n = int(agent.shape[0]), self._num_agents
+        _lib.require_gpu(agent.device, "env.field_of_view")
+        in_fov = torch.empty((B, n, n), dtype=torch.uint8, device=agent.device)
+        torch.ops.dgppo.agent_fov(self._cfg_handle, agent, float(half_angle_deg), in_fov)
+        return in_fov.view(torch.bool)
+
     def _get_graph_hits(self, state, out: Optional[GraphsTuple], lidar_data) -> GraphsTuple:
         what = "get_graph"
         self._require_lidar(what + ": lidar_data")
@@ -547,7 +583,7 @@ class MultiAgentEnv(ABC):
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
     def observe(self, state, t: int, *, sigma: float, dropout: float, seed, env_offset: int = 0,
-                out: Optional[GraphsTuple] = None, occlusion: bool = False) -> GraphsTuple:
+                out: Optional[GraphsTuple] = None, occlusion: bool = False, fov=None) -> GraphsTuple:
         """The OBSERVED graph of the true `state` (get_graph's tuple, obstacles required) at step `t` under the
         range-noise / beam-dropout sensor model of utils/sensor.py, in one HIP launch (torch.ops.dgppo.lidar_observe):
         bit for bit `get_graph(state, lidar_data=lidar_hits(agent, LidarNoise(sigma, dropout, seed,
@@ -559,11 +595,18 @@ class MultiAgentEnv(ABC):
 
         occlusion: obstacles also hide agents from each other -- every agent-agent edge whose receiver has no line of
         sight to its sender goes to the pad node, `mask_unseen(observe(...), line_of_sight(agent, obstacle))` bit for
-        bit, in the same launch (torch.ops.dgppo.lidar_observe_los).  False takes exactly the path without it."""
+        bit, in the same launch (torch.ops.dgppo.lidar_observe_los).  False takes exactly the path without it.
+
+        fov: a half angle in degrees (LidarBicycleTarget and LidarOmniTarget only) -- every agent-agent edge whose sender
+        is outside the receiver's forward cone goes to the pad node as well, `mask_unseen(observe(...),
+        field_of_view(agent, fov) [& line_of_sight(agent, obstacle)])` bit for bit, in the same launch
+        (torch.ops.dgppo.lidar_observe_fov).  The beams stay omnidirectional.  None and 180 take exactly the paths
+        without it."""
         from ..utils.sensor import LidarNoise
 
         what = "observe"
         self._require_lidar(what)
+        fov = self._fov_angle(what, fov)
         sense_range = float(self._params["comm_radius"])
         model = LidarNoise(sigma, dropout, 0, sense_range=sense_range)  # checks sigma and dropout; Phi^-1(dropout)
         t, env_offset = int(t), int(env_offset)
@@ -594,9 +637,14 @@ class MultiAgentEnv(ABC):
         op = torch.ops.dgppo.lidar_observe
         if occlusion:
             op, flags = torch.ops.dgppo.lidar_observe_los, flags | _lib.OBSERVE_SIGHT
-        op(self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
-           iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t, model.sigma / sense_range, model._drop_below,
-           flags, g.nodes, g.edges, g.states, g.receivers, g.senders)
+        head = (self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
+                iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t, model.sigma / sense_range,
+                model._drop_below)
+        if fov is not None:  # the heading envs have no variant: always the fused kernel
+            torch.ops.dgppo.lidar_observe_fov(*head, flags | _lib.OBSERVE_FOV, fov, g.nodes, g.edges, g.states,
+                                              g.receivers, g.senders)
+        else:
+            op(*head, flags, g.nodes, g.edges, g.states, g.receivers, g.senders)
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
     def _observe_chained(self, model, agent, goal, third, t, seed, env_offset, g) -> GraphsTuple:

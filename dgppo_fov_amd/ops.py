@@ -18,6 +18,8 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::lidar_observe  dgppo_lidar_observe  scan, LidarNoise, hits and graph fused: the observed graph of a true state
   dgppo::lidar_sight    dgppo_lidar_sight    which agents see each other past the obstacles (not in the reference)
   dgppo::lidar_observe_los dgppo_lidar_observe_los  lidar_observe with the unseen agent-agent edges sent to the pad node
+  dgppo::agent_fov      dgppo_agent_fov      which agents lie in each other's forward cone, the FoV cost's arithmetic
+  dgppo::lidar_observe_fov dgppo_lidar_observe_fov  lidar_observe_los with the senders outside the receiver's cone masked too
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
@@ -431,6 +433,48 @@ def lidar_sight(cfg: int, agent: Tensor, obstacles: Tensor, visible: Tensor) -> 
 
 @lidar_sight.register_fake
 def _lidar_sight_fake(cfg, agent, obstacles, visible) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::lidar_observe_fov", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
+def lidar_observe_fov(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_dirs: Tensor,
+                      key: Optional[Tensor], seed: int, env_offset: int, t: int, noise_scale: float, drop_below: float,
+                      flags: int, half_angle_deg: float, nodes: Tensor, edges: Tensor, states: Tensor,
+                      receivers: Tensor, senders: Tensor) -> None:
+    """lidar_observe_los that also takes OBSERVE_FOV in `flags`: every agent-agent edge whose sender is outside the
+    receiver's forward cone of `half_angle_deg` (agent_fov) goes to the pad node as well, in the same launch."""
+    _lib.require_gpu(states.device, "dgppo::lidar_observe_fov")
+    io = _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
+                     edges, states, receivers, senders)
+    _lib.check(_lib.load().dgppo_lidar_observe_fov(ctypes.byref(env_cfg(cfg)), ctypes.byref(io),
+                                                   float(half_angle_deg), _stream(states)),
+               "dgppo_lidar_observe_fov")
+
+
+@lidar_observe_fov.register_fake
+def _lidar_observe_fov_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
+                            flags, half_angle_deg, nodes, edges, states, receivers, senders) -> None:
+    return None
+
+
+@torch.library.custom_op("dgppo::agent_fov", mutates_args=("in_fov",))
+def agent_fov(cfg: int, agent: Tensor, half_angle_deg: float, in_fov: Tensor) -> None:
+    """Field of view between the agents of B envs: agent (B, n, sd) rows (columns 2, 3 the heading's cos, sin) ->
+    in_fov (B, n, n) uint8, 1 where sender j is inside receiver i's forward cone of `half_angle_deg` by the FoV cost's
+    arithmetic (the diagonal is 1).  Per-env strides are free; the trailing dims must be contiguous."""
+    _lib.require_gpu(in_fov.device, "dgppo::agent_fov")
+    if in_fov.dtype != torch.uint8:
+        raise ValueError(f"dgppo::agent_fov: in_fov must be uint8, got {in_fov.dtype}")
+    io = _lib.AgentFovIO()
+    io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
+    io.in_fov, io.in_fov_stride = in_fov.data_ptr(), _stride(in_fov, 2)
+    io.half_angle_deg, io.n_env = float(half_angle_deg), int(agent.shape[0])
+    _lib.check(_lib.load().dgppo_agent_fov(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(in_fov)),
+               "dgppo_agent_fov")
+
+
+@agent_fov.register_fake
+def _agent_fov_fake(cfg, agent, half_angle_deg, in_fov) -> None:
     return None
 
 

@@ -261,13 +261,16 @@ class SensorRolloutEngine(RolloutEngine):
     sensor: a callable (alpha (B, n, R), t) -> alpha_obs of the same shape, dtype and device (utils/sensor.py has
     LidarNoise; `lambda a, t: a` reproduces the plain engine bit for bit).  occlusion: obstacles also hide agents from
     each other -- each observed graph then goes through utils.sensor.mask_unseen with env.line_of_sight of the true
-    state, and `sensor` may be None (the identity).  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env with
-    obstacles; no hipGraph capture (a sensor is arbitrary Python)."""
+    state, and `sensor` may be None (the identity).  fov: a half angle in degrees (the envs with a heading) -- the
+    senders outside the receiver's camera cone are hidden too (env.field_of_view, ANDed into the same mask); None and
+    180 mean no cone, and `sensor` may be None here as well.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env
+    with obstacles; no hipGraph capture (a sensor is arbitrary Python)."""
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_DET, sensor=None, init_state=None,
-                 occlusion: bool = False):
-        if sensor is None and occlusion:
+                 occlusion: bool = False, fov=None):
+        fov = env._fov_angle("SensorRolloutEngine", fov)
+        if sensor is None and (occlusion or fov is not None):
             sensor = lambda alpha, t: alpha  # noqa: E731
         if not callable(sensor):
             raise ValueError("SensorRolloutEngine: sensor must be a callable (alpha, t) -> alpha_obs")
@@ -275,7 +278,7 @@ class SensorRolloutEngine(RolloutEngine):
             raise ValueError("SensorRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
         env._require_lidar("SensorRolloutEngine")
         super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
-        self.sensor, self.occlusion = sensor, bool(occlusion)
+        self.sensor, self.occlusion, self.fov = sensor, bool(occlusion), fov
         self.obs_buf = env.empty_graph((self.T, self.B), self.device)  # time-major, like buf
 
     def _observed_at(self, t: int) -> GraphsTuple:
@@ -299,8 +302,12 @@ class SensorRolloutEngine(RolloutEngine):
             alpha_obs = self.sensor(env.lidar_scan(agent, self.obstacles), t)
             seen = env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
                                  lidar_data=env.lidar_hits(agent, alpha_obs))
-            if self.occlusion:
-                mask_unseen(seen, env.line_of_sight(agent, self.obstacles))
+            if self.occlusion or self.fov is not None:
+                vis = env.line_of_sight(agent, self.obstacles) if self.occlusion else None
+                if self.fov is not None:
+                    cone = env.field_of_view(agent, self.fov)
+                    vis = cone if vis is None else vis & cone
+                mask_unseen(seen, vis)
             self._act(t)
             cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
 
@@ -328,7 +335,8 @@ class NoisyLidarRolloutEngine(RolloutEngine):
     a replay with a new key draws new noise -- under the sensor's stream ids (2^62 + 2t, + 1), which cannot collide
     with the policy's (env_offset << 32) | t while env_offset < 2^30 (check_env_offset refuses more); env b's beams
     draw at row env_offset + b.  occlusion: env.observe(..., occlusion=True), the agents hidden from each other by
-    obstacles dropped from every observed graph in the same launch.
+    obstacles dropped from every observed graph in the same launch.  fov: env.observe(..., fov=deg), the senders outside
+    the receiver's camera cone dropped as well (the envs with a heading; None and 180: no cone).
 
     `run` returns the true Rollout; `observed_rollout()` the Rollout the algorithms train on: graph and next_graph
     the observed ones, every other field the true run's.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env
@@ -336,7 +344,7 @@ class NoisyLidarRolloutEngine(RolloutEngine):
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_SAMPLE, sigma: float = 0.0, dropout: float = 0.0,
-                 init_state=None, occlusion: bool = False):
+                 init_state=None, occlusion: bool = False, fov=None):
         from ..utils.sensor import LidarNoise
 
         if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
@@ -344,6 +352,7 @@ class NoisyLidarRolloutEngine(RolloutEngine):
         env._require_lidar("NoisyLidarRolloutEngine")
         model = LidarNoise(sigma, dropout, 0, sense_range=float(env.params["comm_radius"]))  # checks both
         self.sigma, self.dropout, self.occlusion = model.sigma, model.dropout, bool(occlusion)
+        self.fov = env._fov_angle("NoisyLidarRolloutEngine", fov)
         super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
         self.obs = env.empty_graph((self.T + 1, self.B), self.device)  # time-major, like buf
 
@@ -359,7 +368,8 @@ class NoisyLidarRolloutEngine(RolloutEngine):
         env, n = self.env, self.env.num_agents
         s = self.buf.states[t]
         env.observe((s[:, :n], s[:, n:n + env.num_goals], self.obstacles), t, sigma=self.sigma, dropout=self.dropout,
-                    seed=self.key, env_offset=self.env_offset, out=self._observed_at(t), occlusion=self.occlusion)
+                    seed=self.key, env_offset=self.env_offset, out=self._observed_at(t), occlusion=self.occlusion,
+                    fov=self.fov)
 
     def _run(self):
         env = self.env

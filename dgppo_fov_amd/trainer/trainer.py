@@ -69,12 +69,14 @@ class Trainer:
         if self._test_engine is None:
             sensor = getattr(self.algo, "sensor", None)
             occlusion = bool(getattr(self.algo, "occlusion", False))
-            if sensor is not None or occlusion:  # trained under a sensor model: the true costs under sensed control
+            fov = getattr(self.algo, "fov", None)
+            # trained under a sensor model: the true costs under sensed control
+            if sensor is not None or occlusion or fov is not None:
                 sigma, dropout = sensor or (0.0, 0.0)
                 self._test_engine = NoisyLidarRolloutEngine(
                     self.env_test, self.n_env_test, self.env_test.max_episode_steps, self.algo.device,
                     actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sigma=sigma, dropout=dropout,
-                    occlusion=occlusion)
+                    occlusion=occlusion, fov=fov)
             else:
                 self._test_engine = RolloutEngine(self.env_test, self.n_env_test, self.env_test.max_episode_steps,
                                                   self.algo.device, actor=self.algo.actor, mode=RolloutEngine.MODE_DET)

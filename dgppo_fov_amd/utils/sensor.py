@@ -6,7 +6,9 @@ comm_radius), NO_RETURN = 1e6 where nothing is hit (the reference's env/utils.py
 loop, `env.get_graph(state, lidar_data=env.lidar_hits(agent, alpha_obs))` builds a graph from its output.
 
 The other half of an observed graph, who sees whom: `mask_unseen(graph, env.line_of_sight(agent, obstacles))` drops the
-agent-agent edges that an obstacle cuts (`env.observe(..., occlusion=True)` is the fused form).
+agent-agent edges that an obstacle cuts (`env.observe(..., occlusion=True)` is the fused form), and
+`mask_unseen(graph, env.field_of_view(agent, deg))` those whose sender is outside the receiver's camera cone
+(`env.observe(..., fov=deg)`; both at once: `field_of_view(...) & line_of_sight(...)`).
 """
 from __future__ import annotations
 
@@ -33,9 +35,10 @@ def ranges_to_alpha(ranges: torch.Tensor, sense_range: float) -> torch.Tensor:
 
 def mask_unseen(graph, visible: torch.Tensor):
     """Hide the neighbours a receiver cannot see: for every pair with `~visible[..., i, j]` (bool, the graph's batch
-    shape + (n, n), `env.line_of_sight`), edge i * n + j of the leading agent-agent block gets receivers = senders =
-    the pad node (the last node), as out-of-range pairs are stored.  In place on the graph's index tensors; edge
-    features, nodes, states and all other edges are untouched.  Returns the graph."""
+    shape + (n, n): `env.line_of_sight`, `env.field_of_view` or their conjunction), edge i * n + j of the leading
+    agent-agent block gets receivers = senders = the pad node (the last node), as out-of-range pairs are stored.  In
+    place on the graph's index tensors; edge features, nodes, states and all other edges are untouched.  Returns the
+    graph."""
     if not isinstance(visible, torch.Tensor) or visible.dtype != torch.bool:
         raise ValueError("mask_unseen: visible must be a bool tensor")
     recv, send = graph.receivers, graph.senders

@@ -330,6 +330,40 @@ typedef struct dgppo_lidar_sight_io {
 int dgppo_lidar_sight(const dgppo_env_cfg* cfg, const dgppo_lidar_sight_io* io, void* stream);
 int dgppo_lidar_observe_los(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream);
 
+/* Field-of-view neighbour sensing: a receiver sees only the senders inside its forward cone.  For an ordered pair
+ * (receiver i, sender j), i != j, with receiver row (x, y, c, s, ...) -- columns 2, 3 the heading's cosine and sine,
+ * used as given (not normalised) -- in fp32, contraction off, the operation order of the FoV cost (get_cost_omni's
+ * h_a, lidar_omni_target.py:600-620):
+ *   dx = x_j - x_i; dy = y_j - y_i; lx = c dx + s dy; ly = (-s) dx + c dy; nrm = sqrt(lx lx + ly ly)
+ *   in_fov[i, j] = (cb (nrm + 1e-8f) - lx) <= 0,   cb = cos(fp32(half_angle_deg) * fp32(pi / 180))
+ * with cb by the host routine dgppo_env_cfg_finalize uses for the cost's cone, so at half_angle_deg == fov_angle_deg
+ * the sensed cone is the constrained one bit for bit.  The diagonal is 1 without a test; NaN makes a pair unseen (the
+ * comparison fails); coincident agents have nrm = lx = 0 and are seen exactly when cb <= 0 (a quirk of the cost's
+ * formula, kept); there is no range test (comm_radius is one).  0 < half_angle_deg <= 180.
+ *
+ * dgppo_agent_fov: `agent` (n, sd) rows -> `in_fov` (n, n) bytes (0 / 1), per-env strides in elements; one launch,
+ * any n the cfg allows, no obstacles read (n_obs == 0 is served).  Only the engines whose state carries a heading,
+ * DGPPO_ENGINE_BICYCLE and DGPPO_ENGINE_OMNI; every other engine, a half angle outside the domain (NaN included) and
+ * a NULL pointer return DGPPO_EINVAL without a launch; n_env == 0 returns 0.
+ *
+ * dgppo_lidar_observe_fov: dgppo_lidar_observe_los that also accepts DGPPO_OBSERVE_FOV in `flags`: the same graph,
+ * with receivers[e] = senders[e] = the pad node for every agent-agent edge e = i n + j whose pair is not in_fov (with
+ * DGPPO_OBSERVE_SIGHT as well: not visible or not in_fov), in the same launch.  With the bit, the engine and
+ * `half_angle_deg` are checked as above, and exactly 180 means no cone: the launch is that of the other bits alone.
+ * Without the bit `half_angle_deg` is not read and the entry is dgppo_lidar_observe_los.  The other two entries keep
+ * refusing the bit.  No ABI number change (new symbols only). */
+#define DGPPO_OBSERVE_FOV 8
+typedef struct dgppo_agent_fov_io {
+  const float* agent;       int64_t agent_stride;
+  uint8_t* in_fov;          int64_t in_fov_stride;
+  float half_angle_deg;
+  int32_t n_env;
+} dgppo_agent_fov_io;
+
+int dgppo_agent_fov(const dgppo_env_cfg* cfg, const dgppo_agent_fov_io* io, void* stream);
+int dgppo_lidar_observe_fov(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, float half_angle_deg,
+                            void* stream);
+
 /* Host-side helper: `count` obstacle records (count x 16, DGPPO_OBST_FIELDS layout) from HOST arrays center
  * (count x 2), width, height, theta (count each) = Rectangle.create (dgppo/env/obstacle.py:39-56) with the fp32
  * sin / cos and operation order of the reset kernels, so a scene can be assembled without a GPU. */

@@ -32,7 +32,9 @@ ranges with Gaussian noise of std SIGMA world units and beams dropped with proba
 rewards and the costs stay the true ones.  Either flag routes the evaluation through that loop; the summary line then
 names both values.  `--lidar-occlusion` (same envs, with or without the noise flags, no config.yaml entry needed) also
 drops every agent-agent edge whose receiver has no line of sight to its sender past the obstacles from the graphs the
-policy sees (env.line_of_sight, utils/sensor.py mask_unseen)."""
+policy sees (env.line_of_sight, utils/sensor.py mask_unseen).  `--lidar-fov DEG` (LidarBicycleTarget and
+LidarOmniTarget, no config.yaml entry needed, combines with the other three) drops every agent-agent edge whose sender is
+outside the receiver's forward cone of half angle DEG (env.field_of_view)."""
 import argparse
 import os
 
@@ -70,14 +72,19 @@ def test(args):
                      max_grad_norm=2.0, seed=cfg["seed"], use_rnn=cfg.get("use_rnn", True),
                      rnn_layers=cfg.get("rnn_layers", 1), use_lstm=cfg.get("use_lstm", False),
                      batch_size=cfg.get("batch_size", 16384), rnn_step=cfg.get("rnn_step", 16), device=dev)
-    sensed = args.lidar_noise is not None or args.lidar_dropout is not None or args.lidar_occlusion
+    sensed = (args.lidar_noise is not None or args.lidar_dropout is not None or args.lidar_occlusion
+              or args.lidar_fov is not None)
     if sensed:  # refused before anything is loaded or run
         sigma, drop = args.lidar_noise or 0.0, args.lidar_dropout or 0.0
         if env._obstacle_fields() == 0 or env.n_obs == 0 or not hasattr(env, "lidar_scan"):
-            raise SystemExit("--lidar-noise / --lidar-dropout / --lidar-occlusion need a LiDAR env with obstacles; "
-                             f"{type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
+            raise SystemExit("--lidar-noise / --lidar-dropout / --lidar-occlusion / --lidar-fov need a LiDAR env with "
+                             f"obstacles; {type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
         if not sigma >= 0.0 or not 0.0 <= drop <= 1.0:
             raise SystemExit(f"--lidar-noise must be >= 0 and --lidar-dropout in [0, 1], got {sigma} and {drop}")
+        try:
+            fov = env._fov_angle("--lidar-fov", args.lidar_fov)
+        except (ValueError, NotImplementedError) as e:
+            raise SystemExit(str(e))
     if args.cbf is not None and args.video and not args.no_video:  # refused before anything is loaded or run
         if not callable(getattr(algo, "get_Vh", None)):
             raise SystemExit(f"--cbf needs an algorithm with get_Vh; {cfg['algo']} has none")
@@ -117,7 +124,7 @@ def test(args):
         sensor = LidarNoise(sigma, drop, args.seed, sense_range=float(env.params["comm_radius"]))
         eng = SensorRolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset,
                                   actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state,
-                                  occlusion=args.lidar_occlusion)
+                                  occlusion=args.lidar_occlusion, fov=fov)
     else:
         eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
                             mode=mode, init_state=init_state)
@@ -137,7 +144,8 @@ def test(args):
     print(f"reward: {np.mean(rewards):.3f}, min/max reward: {np.min(rewards):.3f}/{np.max(rewards):.3f}, "
           f"cost: {np.mean(costs):.3f}, min/max cost: {np.min(costs):.3f}/{np.max(costs):.3f}, "
           f"safe_rate: {safe_mean * 100:.3f}%" + (f", lidar noise: {sigma:g}, lidar dropout: {drop:g}" if sensed else "") +
-          (", lidar occlusion: on" if args.lidar_occlusion else ""))
+          (", lidar occlusion: on" if args.lidar_occlusion else "") +
+          (f", lidar fov: {args.lidar_fov:g}" if args.lidar_fov is not None else ""))
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(f"{env.num_agents},{args.epi},{env.max_episode_steps},{env.area_size},{env.params['n_obs']},"
@@ -192,6 +200,7 @@ def build_parser():
     parser.add_argument("--lidar-noise", type=float, default=None, metavar="SIGMA")
     parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P")
     parser.add_argument("--lidar-occlusion", action="store_true", default=False)  # obstacles hide agents from each other
+    parser.add_argument("--lidar-fov", type=float, default=None, metavar="DEG")  # half angle of the camera cone
     return parser
 
 

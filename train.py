@@ -10,7 +10,11 @@ launch per step inside the captured rollout): the actor, Vl and Vh all see LiDAR
 world units and beams dropped with probability P, while the env steps, the rewards and the costs stay the true ones.
 The noise is seeded by each rollout's key, so a resumed run continues the same sequence.  `--lidar-occlusion` (same envs
 and algorithms, with or without the noise flags) also lets obstacles hide agents from each other: an agent-agent edge
-whose receiver has no line of sight to its sender is dropped from every graph the networks see."""
+whose receiver has no line of sight to its sender is dropped from every graph the networks see.  `--lidar-fov DEG`
+(LidarBicycleTarget and LidarOmniTarget, same algorithms, combines with the other three) gives every robot a forward
+camera cone of half angle DEG for neighbour sensing: an agent-agent edge whose sender is outside the receiver's cone is
+dropped as well (the LiDAR beams stay omnidirectional); at the env's own `fov_angle_deg` the sensed cone is the
+constrained one bit for bit."""
 import argparse
 import datetime
 import json
@@ -39,6 +43,8 @@ def check_resume_args(args, log_dir, world=None):
     saved.setdefault("_world_size", 1)  # runs saved before the world size was recorded ran on one GPU
     if cur.get("lidar_occlusion"):
         saved.setdefault("lidar_occlusion", False)  # runs saved before the flag existed trained without it
+    if cur.get("lidar_fov") is not None:
+        saved.setdefault("lidar_fov", None)  # likewise
     diff = {k: (saved[k], cur.get(k)) for k in saved if k not in RESUME_FREE and saved[k] != cur.get(k)}
     if diff:
         raise SystemExit("--resume: flags differ from the run's own (saved, given): " +
@@ -86,7 +92,8 @@ def train(args):
         coef_ent=args.coef_ent, rnn_step=args.rnn_step, gamma=0.99, clip_eps=args.clip_eps,
         lagr_init=args.lagr_init, lr_lagr=args.lr_lagr, train_steps=args.steps,
         cbf_schedule=not args.no_cbf_schedule, cost_schedule=args.cost_schedule, device=device,
-        lidar_noise=args.lidar_noise, lidar_dropout=args.lidar_dropout, lidar_occlusion=args.lidar_occlusion)
+        lidar_noise=args.lidar_noise, lidar_dropout=args.lidar_dropout, lidar_occlusion=args.lidar_occlusion,
+        lidar_fov=args.lidar_fov)
     if args.load_checkpoint:
         print(f"> Loading checkpoint from {args.load_checkpoint}, step {args.load_step}")
         algo.load(args.load_checkpoint, args.load_step)
@@ -180,6 +187,8 @@ def build_parser():
     parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P", help="per-beam dropout probability")
     parser.add_argument("--lidar-occlusion", action="store_true", default=False,
                         help="obstacles hide agents from each other in the graphs the networks see")
+    parser.add_argument("--lidar-fov", type=float, default=None, metavar="DEG",
+                        help="half angle of the camera cone: agents outside it are hidden from the receiver")
     return parser
 
 
