@@ -29,6 +29,7 @@ from ..nn import kernels as K
 from ..nn.layers import GraphBatch
 from ..trainer.data import Rollout
 from ..trainer.rollout import NoisyLidarRolloutEngine, RolloutEngine
+from ..utils.sensor import Sensing
 from .module.nets import ActorNet, VhNet, VlNet
 
 
@@ -145,17 +146,13 @@ class DGPPO:
         self._env = env
         # training under the LiDAR sensor model (trainer/rollout.py NoisyLidarRolloutEngine): with either value given,
         # collect and det_rollout return the OBSERVED graphs, so the actor, Vl and Vh all fit what the robots see
-        self.sensor = self._sensor_model(env, lidar_noise, lidar_dropout)
         # lidar_occlusion: obstacles also hide agents from each other in those graphs (env.observe(occlusion=True));
         # on its own it selects the same engine with no noise and no dropout
-        self.occlusion = bool(lidar_occlusion)
-        if self.occlusion and self.sensor is None:
-            self._sensor_model(env, 0.0, 0.0)  # the same refusals as the noise flags
         # lidar_fov: a half angle in degrees -- the senders outside the receiver's camera cone are hidden as well
         # (env.observe(fov=deg), the envs with a heading); on its own it selects the same engine.  None and 180: no cone
-        if lidar_fov is not None and self.sensor is None:
-            self._sensor_model(env, 0.0, 0.0)
-        self.fov = env._fov_angle("lidar_fov", lidar_fov)
+        # ValueError for an algorithm or env that cannot train under them and for values outside their domains
+        self.sensing = Sensing.of(env, "lidar_fov", lidar_noise, lidar_dropout, lidar_occlusion, lidar_fov,
+                                  algo_cls=type(self))
         self.device = torch.device(device) if device is not None else env.device
         self._node_dim, self._edge_dim, self._action_dim, self._n_agents = node_dim, edge_dim, action_dim, n_agents
         self.actor_gnn_layers, self.Vl_gnn_layers, self.Vh_gnn_layers = actor_gnn_layers, Vl_gnn_layers, Vh_gnn_layers
@@ -206,23 +203,20 @@ class DGPPO:
 
     SENSOR_OK = True  # False: the algorithm reads the true state off the rollout's graphs (HCBF-CRPO's get_cost)
 
-    @classmethod
-    def _sensor_model(cls, env, lidar_noise, lidar_dropout):
-        """(sigma, dropout) of the training-time sensor model, or None when neither is given.  ValueError for an
-        algorithm or env that cannot train under it and for values outside LidarNoise's domain."""
-        if lidar_noise is None and lidar_dropout is None:
-            return None
-        from ..utils.sensor import LidarNoise
+    # what self.sensing (utils.sensor.Sensing, None when nothing is sensed) holds, as tests and scripts read it
+    @property
+    def sensor(self):
+        """(sigma, dropout) of the training-time sensor model, or None when neither was given."""
+        s = self.sensing
+        return None if s is None or s.sigma is None else (s.sigma, s.dropout)
 
-        if not cls.SENSOR_OK:
-            raise ValueError(f"{cls.__name__} evaluates env.get_cost on the rollout's graphs, which must be the true "
-                             "ones: lidar_noise / lidar_dropout / lidar_occlusion / lidar_fov are not supported (dgppo, "
-                             "informarl, informarl_lagr are)")
-        if env.ENGINE in env._VMAS_ENGINES or env._obstacle_fields() == 0 or env.n_obs == 0:
-            raise ValueError("lidar_noise / lidar_dropout / lidar_occlusion / lidar_fov need a LiDAR env with obstacles; "
-                             f"{type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
-        model = LidarNoise(lidar_noise or 0.0, lidar_dropout or 0.0, 0, sense_range=float(env.params["comm_radius"]))
-        return model.sigma, model.dropout
+    @property
+    def occlusion(self) -> bool:
+        return self.sensing is not None and self.sensing.occlusion
+
+    @property
+    def fov(self) -> Optional[float]:
+        return None if self.sensing is None else self.sensing.fov
 
     # ---- reference properties ------------------------------------------------------------------
     @property
@@ -323,7 +317,7 @@ class DGPPO:
     def sensed(self) -> bool:
         """Whether collect and det_rollout return observed graphs (a sensor model, occlusion, a field of view, or any
         of them together)."""
-        return self.sensor is not None or self.occlusion or self.fov is not None
+        return self.sensing is not None
 
     def _rollout_lanes(self, n_env: int) -> int:
         """Env slices on separate streams (RolloutEngine lanes): DGPPO_ROLLOUT_LANES when the slices are
@@ -335,11 +329,9 @@ class DGPPO:
         k = (n_env, mode)
         if k not in self._engines:
             if self.sensed:
-                sigma, dropout = self.sensor or (0.0, 0.0)
                 eng = NoisyLidarRolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                               env_offset=self.rank * n_env, actor=self.actor, mode=mode,
-                                              sigma=sigma, dropout=dropout, occlusion=self.occlusion,
-                                              fov=self.fov)
+                                              sensing=self.sensing)
             else:
                 eng = RolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                     env_offset=self.rank * n_env, actor=self.actor, mode=mode,

@@ -115,7 +115,8 @@ __device__ __forceinline__ bool rect_inside(const float* rec, float px, float py
   return down || up || (corner && circle);
 }
 
-// Rectangle.raytracing for one ray against the 4 edges of one obstacle.
+// Rectangle.raytracing for one ray against one edge (e of 4) of one obstacle: the edge's alpha as the reference's
+// minimum sees it, and in `valid` whether the edge is crossed (alpha and beta both in [0, 1]).
 //
 // Exactly the reference's result, with most IEEE divisions skipped: an edge whose alpha or beta is
 // PROVABLY outside [0, 1] contributes exactly 1e6 in the reference (valid = 0 -> 0*alpha + 1e6), so
@@ -124,39 +125,40 @@ __device__ __forceinline__ bool rect_inside(const float* rec, float px, float py
 // only); everything else -- including det == 0 and NaN inputs, which make the reference's alpha NaN --
 // takes the full divide-and-compare path.  The per-ray terms ax = x1-x2, ay = y1-y2 and per-edge
 // vectors (x4-x3, y4-y3) are exactly the reference's sub-expressions, hoisted.
+__device__ __forceinline__ float rect_edge(const float* rec, const float* evec, int e, float x1, float y1, float ax,
+                                           float ay, bool& valid) {
+  const float x3 = rec[8 + 2 * e], y3 = rec[9 + 2 * e];
+  const float exe = evec[2 * e], eye = evec[2 * e + 1];  // x4 - x3, y4 - y3
+  const float px = x1 - x3, py = y1 - y3;
+  const float det = ax * eye - ay * exe;
+  const float na = eye * px - exe * py;
+  const float nb = (-ay) * px + ax * py;
+  const float adet = fabsf(det);
+  valid = false;
+  if (!(adet > 0.0f)) return __builtin_nanf("");  // det == 0 (sign 0) or NaN: the reference's alpha is NaN
+  const float cl = adet < 1e-7f ? 1e-7f : (adet > 1e7f ? 1e7f : adet);
+  const float detc = det < 0.0f ? -cl : cl;
+  const float lim = cl * 1.001f;
+  const float ana = fabsf(na), anb = fabsf(nb);
+  const bool finite = ana <= 3.0e38f && anb <= 3.0e38f;
+  const bool neg_d = detc < 0.0f;
+  const bool out = finite && (ana > lim || anb > lim || (ana >= 1e-30f && ((na < 0.0f) != neg_d)) ||
+                              (anb >= 1e-30f && ((nb < 0.0f) != neg_d)));
+  if (out) return 1e6f;
+  const float alpha = na / detc;
+  const float beta = nb / detc;
+  valid = (alpha <= 1.0f) && (alpha >= 0.0f) && (beta <= 1.0f) && (beta >= 0.0f);
+  return valid ? alpha + 0.0f : (alpha != alpha ? alpha : 1e6f);
+}
+
+// the reference's result for the rectangle: the NaN-propagating minimum over its 4 edges
 __device__ __forceinline__ float rect_raytrace(const float* rec, const float* evec, float x1, float y1, float ax,
                                                float ay) {
   float best = 0.0f;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const float x3 = rec[8 + 2 * e], y3 = rec[9 + 2 * e];
-    const float exe = evec[2 * e], eye = evec[2 * e + 1];  // x4 - x3, y4 - y3
-    const float px = x1 - x3, py = y1 - y3;
-    const float det = ax * eye - ay * exe;
-    const float na = eye * px - exe * py;
-    const float nb = (-ay) * px + ax * py;
-    const float adet = fabsf(det);
-    float a;
-    if (!(adet > 0.0f)) {
-      a = __builtin_nanf("");  // det == 0 (sign 0) or NaN: the reference's alpha is NaN
-    } else {
-      const float cl = adet < 1e-7f ? 1e-7f : (adet > 1e7f ? 1e7f : adet);
-      const float detc = det < 0.0f ? -cl : cl;
-      const float lim = cl * 1.001f;
-      const float ana = fabsf(na), anb = fabsf(nb);
-      const bool finite = ana <= 3.0e38f && anb <= 3.0e38f;
-      const bool neg_d = detc < 0.0f;
-      const bool out = finite && (ana > lim || anb > lim || (ana >= 1e-30f && ((na < 0.0f) != neg_d)) ||
-                                  (anb >= 1e-30f && ((nb < 0.0f) != neg_d)));
-      if (out) {
-        a = 1e6f;
-      } else {
-        const float alpha = na / detc;
-        const float beta = nb / detc;
-        const bool valid = (alpha <= 1.0f) && (alpha >= 0.0f) && (beta <= 1.0f) && (beta >= 0.0f);
-        a = valid ? alpha + 0.0f : (alpha != alpha ? alpha : 1e6f);
-      }
-    }
+    bool valid;
+    const float a = rect_edge(rec, evec, e, x1, y1, ax, ay, valid);
     best = e == 0 ? a : min_nan(best, a);
   }
   return best;
@@ -516,6 +518,41 @@ __device__ __forceinline__ uint64_t sort_key(float a, int r) {
   return ((uint64_t)ord << 32) | (uint32_t)r;
 }
 
+// The sensing stages, one function each: the sensor kernels (scan | hits | sight | fov | the fused observe) are
+// compositions of these, which is what makes the fused kernel equal the chained ones.  lidar_scan below shares
+// beam_point; its own cast and rank loops are the same arithmetic, kept where sharing moved the step kernels' code.
+
+// One beam from (sx, sy) along (dx, dy) against the staged obstacles: min_nan over them of rect_raytrace, times
+// (1 - *is_in) -- the value the scan ranks.  is_in is read after the obstacle loop, where the kernels always read it.
+__device__ __forceinline__ float beam_alpha(const float* obst, const float* evec, int O, float sx, float sy, float dx,
+                                            float dy, const float* is_in) {
+  const float ex = sx + dx;
+  const float ey = sy + dy;
+  const float ax = sx - ex, ay = sy - ey;
+  float a = 0.0f;
+#pragma unroll 1
+  for (int o = 0; o < O; ++o) {
+    const float ao = rect_raytrace(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
+    a = o == 0 ? ao : min_nan(a, ao);
+  }
+  return a * (1.0f - *is_in);
+}
+
+// The hit point of that beam at alpha a: start + (end - start) * a with the end formed first, as the reference
+// does (sx + dx * a differs in fp32).
+__device__ __forceinline__ float2 beam_point(float sx, float sy, float dx, float dy, float a) {
+  const float ex = sx + dx;
+  const float ey = sy + dy;
+  return make_float2(sx + (ex - sx) * a, sy + (ey - sy) * a);
+}
+
+// The stable NaN-last rank of a beam among the R of its agent: how many sort_keys of the row are smaller.
+__device__ __forceinline__ int rank_below(const uint64_t* row, int R, uint64_t key) {
+  int rank = 0;
+  for (int j = 0; j < R; ++j) rank += row[j] < key ? 1 : 0;
+  return rank;
+}
+
 template <int SD, class D>
 __device__ __forceinline__ void lidar_scan(const D& d, const float* ray_dirs, float* lds, const Carve& cv, int tid,
                                            int nthr) {
@@ -695,14 +732,13 @@ __device__ __forceinline__ void lidar_scan(const D& d, const float* ray_dirs, fl
       const int i = p / R, r = p - (p / R) * R;
       const float sx = nxt[i * SD + 0], sy = nxt[i * SD + 1];
       const float4 rc = rayc[r];
-      const float ex = sx + rc.x;
-      const float ey = sy + rc.y;
       const uint32_t e = aenc[p];
       float a = e == 0u ? __builtin_nanf("") : __uint_as_float(e - 1u);
       a = a * (1.0f - lds[cv.isin + i]);
       keys[p] = sort_key(a, r);
-      hpt[2 * p + 0] = sx + (ex - sx) * a;
-      hpt[2 * p + 1] = sy + (ey - sy) * a;
+      const float2 h = beam_point(sx, sy, rc.x, rc.y, a);
+      hpt[2 * p + 0] = h.x;
+      hpt[2 * p + 1] = h.y;
     }
   } else {
 #pragma unroll 1
@@ -713,15 +749,16 @@ __device__ __forceinline__ void lidar_scan(const D& d, const float* ray_dirs, fl
     const float ex = sx + ray_dirs[2 * r + 0];
     const float ey = sy + ray_dirs[2 * r + 1];
     const float ax = sx - ex, ay = sy - ey;
-    float a = 0.0f;
+    float a = 0.0f;  // beam_alpha, in place: through the function the benchmarked kernels' instruction text changes
     for (int o = 0; o < O; ++o) {
       const float ao = rect_raytrace(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
       a = o == 0 ? ao : min_nan(a, ao);
     }
     a = a * (1.0f - lds[cv.isin + i]);
     keys[p] = sort_key(a, r);
-    hpt[2 * p + 0] = sx + (ex - sx) * a;
-    hpt[2 * p + 1] = sy + (ey - sy) * a;
+    const float2 h = beam_point(sx, sy, ray_dirs[2 * r + 0], ray_dirs[2 * r + 1], a);
+    hpt[2 * p + 0] = h.x;
+    hpt[2 * p + 1] = h.y;
   }
   }
   __syncthreads();
@@ -731,7 +768,7 @@ __device__ __forceinline__ void lidar_scan(const D& d, const float* ray_dirs, fl
     const int i = p / R;
     const uint64_t key = keys[p];
     const uint64_t* row = keys + i * R;
-    int rank = 0;
+    int rank = 0;  // rank_below, in place: with the unroll the benchmarked kernels were tuned with
 #pragma unroll 8
     for (int j = 0; j < R; ++j) rank += row[j] < key ? 1 : 0;
     if (rank < k) {
@@ -3016,8 +3053,7 @@ __device__ __forceinline__ Carve scan_carve() {
 }
 constexpr int kScanLds = kMaxObs * DGPPO_OBST_FIELDS + kMaxObs * 8 + 4;
 
-// dgppo_lidar_scan: one wave per (env, agent), lanes over rays.  alpha[r] = the value lidar_scan ranks: min_nan over
-// obstacles of rect_raytrace, times (1 - is_in) -- the R > 32 branch of lidar_scan, ray by ray.
+// dgppo_lidar_scan: one wave per (env, agent), lanes over rays.  alpha[r] = beam_alpha, ray by ray.
 __global__ __launch_bounds__(64) void lidar_alpha_kernel(dgppo_env_cfg cfg, dgppo_lidar_scan_io io) {
   __shared__ __attribute__((aligned(16))) float lds[kScanLds];
   const int n = cfg.n_agents, O = cfg.n_obs, R = cfg.n_rays, sd = cfg.state_dim;
@@ -3025,34 +3061,26 @@ __global__ __launch_bounds__(64) void lidar_alpha_kernel(dgppo_env_cfg cfg, dgpp
   const int64_t env = blockIdx.x / n;
   const int i = blockIdx.x - (int)env * n;
   const Carve cv = scan_carve();
+  float* obst = lds + cv.obst;
+  float* evec = lds + cv.evec;
+  float* xy = lds + cv.nxt;
+  float* isin = lds + cv.isin;
   const float* ob = io.obstacles + env * io.obstacles_stride;
-  for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) lds[cv.obst + idx] = ob[idx];
-  if (lane < 2) lds[cv.nxt + lane] = io.agent[env * io.agent_stride + i * sd + lane];
+  for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) obst[idx] = ob[idx];
+  if (lane < 2) xy[lane] = io.agent[env * io.agent_stride + i * sd + lane];
   __syncthreads();
   stage_edge_vectors(O, lds, cv, lane, 64);
   if (lane == 0) agent_is_inside(O, lds, cv, 2, 0);
   __syncthreads();
-  const float* obst = lds + cv.obst;
-  const float* evec = lds + cv.evec;
-  const float sx = lds[cv.nxt], sy = lds[cv.nxt + 1];
+  const float sx = xy[0], sy = xy[1];
   float* out = io.alpha + env * io.alpha_stride + (int64_t)i * R;
 #pragma unroll 1
-  for (int r = lane; r < R; r += 64) {
-    const float ex = sx + io.ray_dirs[2 * r + 0];
-    const float ey = sy + io.ray_dirs[2 * r + 1];
-    const float ax = sx - ex, ay = sy - ey;
-    float a = 0.0f;
-#pragma unroll 1
-    for (int o = 0; o < O; ++o) {
-      const float ao = rect_raytrace(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
-      a = o == 0 ? ao : min_nan(a, ao);
-    }
-    out[r] = a * (1.0f - lds[cv.isin]);
-  }
+  for (int r = lane; r < R; r += 64)
+    out[r] = beam_alpha(obst, evec, O, sx, sy, io.ray_dirs[2 * r + 0], io.ray_dirs[2 * r + 1], isin);
 }
 
-// dgppo_lidar_hits: one wave per (env, agent).  The stable NaN-last rank of the caller's alphas by counting smaller
-// sort_keys (lidar_scan's last loop), the hit point by lidar_scan's expression.
+// dgppo_lidar_hits: one wave per (env, agent): rank_below over the sort_keys of the caller's alphas, beam_point for
+// the top k.
 __global__ __launch_bounds__(64) void lidar_hits_kernel(dgppo_env_cfg cfg, dgppo_lidar_hits_io io) {
   __shared__ uint64_t keys[kMaxRays];
   const int n = cfg.n_agents, R = cfg.n_rays, k = cfg.top_k, sd = cfg.state_dim;
@@ -3067,15 +3095,11 @@ __global__ __launch_bounds__(64) void lidar_hits_kernel(dgppo_env_cfg cfg, dgppo
   float* hits = io.hits + env * io.hits_stride + (int64_t)i * k * 2;
 #pragma unroll 1
   for (int r = lane; r < R; r += 64) {
-    const uint64_t key = keys[r];
-    int rank = 0;
-    for (int j = 0; j < R; ++j) rank += keys[j] < key ? 1 : 0;
+    const int rank = rank_below(keys, R, keys[r]);
     if (rank < k) {
-      const float a = al[r];
-      const float ex = sx + io.ray_dirs[2 * r + 0];
-      const float ey = sy + io.ray_dirs[2 * r + 1];
-      hits[rank * 2 + 0] = sx + (ex - sx) * a;
-      hits[rank * 2 + 1] = sy + (ey - sy) * a;
+      const float2 h = beam_point(sx, sy, io.ray_dirs[2 * r + 0], io.ray_dirs[2 * r + 1], al[r]);
+      hits[rank * 2 + 0] = h.x;
+      hits[rank * 2 + 1] = h.y;
     }
   }
 }
@@ -3126,38 +3150,17 @@ __global__ __launch_bounds__(BLOCK) void env_graph_hits_kernel(dgppo_env_cfg cfg
 }
 
 // ---- line of sight between agents -----------------------------------------------------------------
-// Does the segment from (x1, y1) to (x1 - ax, y1 - ay) cross an edge of the rectangle?  rect_raytrace's per-edge
-// arithmetic and conservative `out` screen, asking "is any edge valid" instead of taking the NaN-propagating
-// minimum: det == 0 and NaN make that edge invalid (the reference's alpha is then NaN or infinite, and every
-// comparison of `valid` fails), an edge the screen proves outside [0, 1] is invalid without the divisions.
+// Does the segment from (x1, y1) to (x1 - ax, y1 - ay) cross an edge of the rectangle?  rect_edge asked "is any edge
+// valid" instead of for the NaN-propagating minimum: det == 0 and NaN make that edge invalid (the reference's alpha
+// is then NaN or infinite, and every comparison of `valid` fails), an edge the screen proves outside [0, 1] is invalid
+// without the divisions.
 __device__ __forceinline__ bool rect_blocks(const float* rec, const float* evec, float x1, float y1, float ax,
                                             float ay) {
   bool any = false;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const float x3 = rec[8 + 2 * e], y3 = rec[9 + 2 * e];
-    const float exe = evec[2 * e], eye = evec[2 * e + 1];  // x4 - x3, y4 - y3
-    const float px = x1 - x3, py = y1 - y3;
-    const float det = ax * eye - ay * exe;
-    const float na = eye * px - exe * py;
-    const float nb = (-ay) * px + ax * py;
-    const float adet = fabsf(det);
-    bool valid = false;
-    if (adet > 0.0f) {
-      const float cl = adet < 1e-7f ? 1e-7f : (adet > 1e7f ? 1e7f : adet);
-      const float detc = det < 0.0f ? -cl : cl;
-      const float lim = cl * 1.001f;
-      const float ana = fabsf(na), anb = fabsf(nb);
-      const bool finite = ana <= 3.0e38f && anb <= 3.0e38f;
-      const bool neg_d = detc < 0.0f;
-      const bool out = finite && (ana > lim || anb > lim || (ana >= 1e-30f && ((na < 0.0f) != neg_d)) ||
-                                  (anb >= 1e-30f && ((nb < 0.0f) != neg_d)));
-      if (!out) {
-        const float alpha = na / detc;
-        const float beta = nb / detc;
-        valid = (alpha <= 1.0f) && (alpha >= 0.0f) && (beta <= 1.0f) && (beta >= 0.0f);
-      }
-    }
+    bool valid;
+    rect_edge(rec, evec, e, x1, y1, ax, ay, valid);
     any = any | valid;
   }
   return any;
@@ -3176,33 +3179,6 @@ __device__ __forceinline__ bool pair_blocked(int O, const float* obst, const flo
   return blocked;
 }
 
-// dgppo_lidar_sight: one wave per env, lanes striding over the n * n ordered (receiver, sender) pairs (any n: the
-// pair loop runs ceil(n * n / 64) passes).  Obstacle records and edge vectors staged as in lidar_alpha_kernel, the
-// agents' positions behind them.  visible[i, j] = no edge of any obstacle is valid for the segment i -> j; the
-// diagonal is 1 without a test.
-constexpr int kSightLds = kScanLds + 2 * kMaxAgents;
-__global__ __launch_bounds__(64) void lidar_sight_kernel(dgppo_env_cfg cfg, dgppo_lidar_sight_io io) {
-  __shared__ __attribute__((aligned(16))) float lds[kSightLds];
-  const int n = cfg.n_agents, O = cfg.n_obs, sd = cfg.state_dim;
-  const int lane = threadIdx.x;
-  const int64_t env = blockIdx.x;
-  const Carve cv = scan_carve();
-  float* pos = lds + kScanLds;  // (n, 2)
-  const float* ob = io.obstacles + env * io.obstacles_stride;
-  const float* ag = io.agent + env * io.agent_stride;
-  for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) lds[cv.obst + idx] = ob[idx];
-  for (int idx = lane; idx < 2 * n; idx += 64) pos[idx] = ag[(idx >> 1) * sd + (idx & 1)];
-  __syncthreads();
-  stage_edge_vectors(O, lds, cv, lane, 64);
-  __syncthreads();
-  uint8_t* out = io.visible + env * io.visible_stride;
-#pragma unroll 1
-  for (int q = lane; q < n * n; q += 64) {
-    const int i = q / n, j = q - i * n;
-    out[q] = (i == j || !pair_blocked(O, lds + cv.obst, lds + cv.evec, pos, 2, i, j)) ? 1 : 0;
-  }
-}
-
 // ---- field of view between agents ------------------------------------------------------------------
 // Is agent j inside agent i's forward cone (rows of `rows`, row stride rs: x, y, heading cos, heading sin)?  The FoV
 // cost's arithmetic and operation order (cq[2] of the step kernels, get_cost_omni's h_a), cb the cone's cosine: the
@@ -3216,9 +3192,54 @@ __device__ __forceinline__ bool pair_in_fov(const float* rows, int rs, int i, in
   return (cb * (nrm + 1e-8f) - lx) <= 0.0f;
 }
 
-// dgppo_agent_fov: one wave per env, lanes striding over the n * n ordered (receiver, sender) pairs as in
-// lidar_sight_kernel; the first four columns of the agent rows staged in LDS.  in_fov[i, j] = pair_in_fov, the
-// diagonal 1 without a test.  cb comes from the host (fov_cos, dgppo_env_cfg_finalize's routine).
+// ---- who sees whom: the one predicate and the one loop over the ordered pairs -------------------------
+// Is sender j hidden from receiver i: cut off by an obstacle (SIGHT), outside i's cone (FOV), or either.
+template <bool SIGHT, bool FOV>
+__device__ __forceinline__ bool pair_unseen(int O, const float* obst, const float* evec, const float* rows, int rs,
+                                            int i, int j, float cb) {
+  bool hide = false;
+  if constexpr (SIGHT) hide = pair_blocked(O, obst, evec, rows, rs, i, j);
+  if constexpr (FOV) hide = hide | !pair_in_fov(rows, rs, i, j, cb);
+  return hide;
+}
+
+// out[i * n + j] = `hidden` where pair_unseen, else 1 - hidden, over the n * n ordered (receiver, sender) pairs, the
+// threads striding over them (any n: ceil(n * n / nthr) passes).  The diagonal is seen without a test.
+template <bool SIGHT, bool FOV>
+__device__ __forceinline__ void mark_pairs(uint8_t* out, uint8_t hidden, int n, int O, const float* obst,
+                                           const float* evec, const float* rows, int rs, float cb, int tid, int nthr) {
+#pragma unroll 1
+  for (int q = tid; q < n * n; q += nthr) {
+    const int i = q / n, j = q - i * n;
+    const bool hide = i != j && pair_unseen<SIGHT, FOV>(O, obst, evec, rows, rs, i, j, cb);
+    out[q] = hide ? hidden : 1 - hidden;
+  }
+}
+
+// dgppo_lidar_sight: one wave per env.  Obstacle records and edge vectors staged as in lidar_alpha_kernel, the
+// agents' positions behind them.  visible = mark_pairs<SIGHT> with hidden = 0.
+constexpr int kSightLds = kScanLds + 2 * kMaxAgents;
+__global__ __launch_bounds__(64) void lidar_sight_kernel(dgppo_env_cfg cfg, dgppo_lidar_sight_io io) {
+  __shared__ __attribute__((aligned(16))) float lds[kSightLds];
+  const int n = cfg.n_agents, O = cfg.n_obs, sd = cfg.state_dim;
+  const int lane = threadIdx.x;
+  const int64_t env = blockIdx.x;
+  const Carve cv = scan_carve();
+  float* obst = lds + cv.obst;
+  float* evec = lds + cv.evec;
+  float* pos = lds + kScanLds;  // (n, 2)
+  const float* ob = io.obstacles + env * io.obstacles_stride;
+  const float* ag = io.agent + env * io.agent_stride;
+  for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) obst[idx] = ob[idx];
+  for (int idx = lane; idx < 2 * n; idx += 64) pos[idx] = ag[(idx >> 1) * sd + (idx & 1)];
+  __syncthreads();
+  stage_edge_vectors(O, lds, cv, lane, 64);
+  __syncthreads();
+  mark_pairs<true, false>(io.visible + env * io.visible_stride, 0, n, O, obst, evec, pos, 2, 0.0f, lane, 64);
+}
+
+// dgppo_agent_fov: one wave per env; the first four columns of the agent rows staged in LDS.  in_fov =
+// mark_pairs<FOV> with hidden = 0.  cb comes from the host (fov_cos, dgppo_env_cfg_finalize's routine).
 __global__ __launch_bounds__(64) void agent_fov_kernel(dgppo_env_cfg cfg, dgppo_agent_fov_io io, float cb) {
   __shared__ __attribute__((aligned(16))) float rows[4 * kMaxAgents];
   const int n = cfg.n_agents, sd = cfg.state_dim;
@@ -3227,27 +3248,21 @@ __global__ __launch_bounds__(64) void agent_fov_kernel(dgppo_env_cfg cfg, dgppo_
   const float* ag = io.agent + env * io.agent_stride;
   for (int idx = lane; idx < 4 * n; idx += 64) rows[idx] = ag[(idx >> 2) * sd + (idx & 3)];
   __syncthreads();
-  uint8_t* out = io.in_fov + env * io.in_fov_stride;
-#pragma unroll 1
-  for (int q = lane; q < n * n; q += 64) {
-    const int i = q / n, j = q - i * n;
-    out[q] = (i == j || pair_in_fov(rows, 4, i, j, cb)) ? 1 : 0;
-  }
+  mark_pairs<false, true>(io.in_fov + env * io.in_fov_stride, 0, n, 0, nullptr, nullptr, rows, 4, cb, lane, 64);
 }
 
 // dgppo_lidar_observe: scan | LidarNoise | hits | graph in one launch, one workgroup per env.  The beams of all agents
-// are cast by lidar_alpha_kernel's arithmetic into LDS (the alphas in the carve's hpt region, their sort keys in its
-// alpha region), the sensor model (utils/sensor.py LidarNoise.__call__, op for op) edits each alpha as it is made,
-// lidar_hits_kernel's counting rank puts the top-k hit points into lds + cv.hits, and graph_of_staged_hits writes
-// the graph.  Every input row is staged before the first store.
-// SIGHT (dgppo_lidar_observe_los with DGPPO_OBSERVE_SIGHT): the ordered agent pairs are tested by lidar_sight_kernel's
-// arithmetic into a byte mask in the carve's dist region (dead in this kernel; n * n bytes <= its 2 n * n floats), and
-// after the graph is written and a workgroup barrier the blocked pairs' receivers / senders are overwritten with the
-// pad node.  The graph writers are untouched.
-// FOV (dgppo_lidar_observe_fov with DGPPO_OBSERVE_FOV; the engines with a heading only): pair_in_fov on the agent rows
-// staged in nxt ORs "outside the receiver's cone" into the same byte mask, for the same post-pass.  The cone's cosine
-// arrives as cfg.c_cos_fov: the entry launches with a copy of the cfg that holds the sensed cone there (this kernel
-// evaluates no cost, so nothing else reads the field), which leaves the kernel's arguments as they were.
+// are cast by beam_alpha into LDS (the alphas in the carve's hpt region, their sort keys in its alpha region), the
+// sensor model (utils/sensor.py LidarNoise.__call__, op for op) edits each alpha as it is made, rank_below and
+// beam_point put the top-k hit points into lds + cv.hits, and graph_of_staged_hits writes the graph.  Every input
+// row is staged before the first store.
+// SIGHT (dgppo_lidar_observe_los with DGPPO_OBSERVE_SIGHT) and FOV (dgppo_lidar_observe_fov with DGPPO_OBSERVE_FOV; the
+// engines with a heading only): mark_pairs<SIGHT, FOV> on the agent rows staged in nxt, hidden = 1, into a byte mask
+// in the carve's dist region (dead in this kernel; n * n bytes <= its 2 n * n floats), and after the graph is written
+// and a workgroup barrier the hidden pairs' receivers / senders are overwritten with the pad node.  The graph writers
+// are untouched.  The cone's cosine arrives as cfg.c_cos_fov: the entry launches with a copy of the cfg that holds the
+// sensed cone there (this kernel evaluates no cost, so nothing else reads the field), which leaves the kernel's
+// arguments as they were.
 template <int ENGINE, int GOAL, int SD, int BLOCK, bool SIGHT = false, bool FOV = false>
 __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg, dgppo_lidar_observe_io io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -3277,16 +3292,7 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
   uint8_t* unseen = reinterpret_cast<uint8_t*>(lds + cv.dist);     // (n, n), SIGHT / FOV only
   if constexpr (SIGHT || FOV) {
     static_assert(!FOV || ENGINE == DGPPO_ENGINE_BICYCLE || ENGINE == DGPPO_ENGINE_OMNI, "FOV needs a heading");
-#pragma unroll 1
-    for (int q = tid; q < n * n; q += BLOCK) {
-      const int i = q / n, j = q - i * n;
-      bool hide = false;
-      if (i != j) {
-        if constexpr (SIGHT) hide = pair_blocked(O, obst, evec, nxt, SD, i, j);
-        if constexpr (FOV) hide = hide | !pair_in_fov(nxt, SD, i, j, cfg.c_cos_fov);
-      }
-      unseen[q] = hide ? 1 : 0;
-    }
+    mark_pairs<SIGHT, FOV>(unseen, 1, n, O, obst, evec, nxt, SD, cfg.c_cos_fov, tid, BLOCK);
   }
   const uint64_t seed = io.seed_ptr ? *io.seed_ptr : io.seed;
   const uint64_t stream = ((uint64_t)1 << 62) + 2 * (uint64_t)io.t;  // LidarNoise.STREAM_BASE + 2 t (+ 1: dropout)
@@ -3294,17 +3300,8 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
 #pragma unroll 1
   for (int q = tid; q < n * R; q += BLOCK) {
     const int i = q / R, r = q - i * R;
-    const float sx = nxt[i * SD + 0], sy = nxt[i * SD + 1];
-    const float ex = sx + io.ray_dirs[2 * r + 0];
-    const float ey = sy + io.ray_dirs[2 * r + 1];
-    const float ax = sx - ex, ay = sy - ey;
-    float a = 0.0f;
-#pragma unroll 1
-    for (int o = 0; o < O; ++o) {
-      const float ao = rect_raytrace(obst + o * DGPPO_OBST_FIELDS, evec + o * 8, sx, sy, ax, ay);
-      a = o == 0 ? ao : min_nan(a, ao);
-    }
-    a = a * (1.0f - lds[cv.isin + i]);
+    const float a = beam_alpha(obst, evec, O, nxt[i * SD + 0], nxt[i * SD + 1], io.ray_dirs[2 * r + 0],
+                               io.ray_dirs[2 * r + 1], lds + cv.isin + i);
     float seen = a;
     if (io.flags & DGPPO_OBSERVE_NOISE) {
       const float x = a + noise::normal_at(e0 + q, seed, stream) * io.noise_scale;
@@ -3324,16 +3321,12 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
   for (int q = tid; q < n * R; q += BLOCK) {
     const int i = q / R, r = q - i * R;
     const uint64_t* row = keys + i * R;
-    const uint64_t key = row[r];
-    int rank = 0;
-    for (int j = 0; j < R; ++j) rank += row[j] < key ? 1 : 0;
+    const int rank = rank_below(row, R, row[r]);
     if (rank < k) {
-      const float a = alpha[q];
-      const float sx = nxt[i * SD + 0], sy = nxt[i * SD + 1];
-      const float ex = sx + io.ray_dirs[2 * r + 0];
-      const float ey = sy + io.ray_dirs[2 * r + 1];
-      hits[(i * k + rank) * 2 + 0] = sx + (ex - sx) * a;
-      hits[(i * k + rank) * 2 + 1] = sy + (ey - sy) * a;
+      const float2 h = beam_point(nxt[i * SD + 0], nxt[i * SD + 1], io.ray_dirs[2 * r + 0], io.ray_dirs[2 * r + 1],
+                                  alpha[q]);
+      hits[(i * k + rank) * 2 + 0] = h.x;
+      hits[(i * k + rank) * 2 + 1] = h.y;
     }
   }
   __syncthreads();

@@ -527,24 +527,6 @@ class MultiAgentEnv(ABC):
         torch.ops.dgppo.lidar_sight(self._cfg_handle, agent, ob, visible)
         return visible.view(torch.bool)
 
-    _HEADING_ENGINES = (_lib.DGPPO_ENGINE_BICYCLE, _lib.DGPPO_ENGINE_OMNI)
-
-    def _fov_angle(self, what: str, fov) -> Optional[float]:
-        """The half angle of a sensing cone in degrees, or None for no cone (`fov` None or exactly 180).  A cone needs
-        an env whose state carries a heading (LidarBicycleTarget, LidarOmniTarget) and 0 < fov <= 180: ValueError
-        otherwise (NotImplementedError for the VMAS envs), before the GPU is touched."""
-        if fov is None:
-            return None
-        if self.ENGINE in self._VMAS_ENGINES:
-            raise NotImplementedError(f"{what}: the VMAS envs have no field-of-view sensor model")
-        if self.ENGINE not in self._HEADING_ENGINES:
-            raise ValueError(f"{what}: a field of view needs a heading in the state (LidarBicycleTarget, "
-                             f"LidarOmniTarget); {type(self).__name__} has no heading")
-        deg = float(fov)
-        if not 0.0 < deg <= 180.0:
-            raise ValueError(f"{what}: the half angle must be in (0, 180] degrees, got {fov}")
-        return None if deg == 180.0 else deg
-
     def field_of_view(self, agent_states: torch.Tensor, half_angle_deg: float) -> torch.Tensor:
         """Which agents lie in each other's camera cone (torch.ops.dgppo.agent_fov): bool (B, n, n), entry [b, i, j]
         True where agent j of env b is inside the forward cone of half angle `half_angle_deg` (0 < deg <= 180) around
@@ -554,8 +536,10 @@ class MultiAgentEnv(ABC):
         cosine is <= 0 (the formula's quirk), and there is no range test.  Only the envs with a heading; no obstacles
         are needed.  `utils.sensor.mask_unseen(graph, in_fov)` applies it to a graph; `observe(..., fov=deg)` does both
         in its one launch."""
+        from ..utils.sensor import cone_angle
+
         what = "field_of_view"
-        self._fov_angle(what, float("nan") if half_angle_deg is None else half_angle_deg)  # the env, then the domain
+        cone_angle(self, what, float("nan") if half_angle_deg is None else half_angle_deg)  # the env, then the domain
         agent = self._sensor_agents(what, agent_states)
         B, n = int(agent.shape[0]), self._num_agents
         _lib.require_gpu(agent.device, "env.field_of_view")
@@ -602,13 +586,12 @@ class MultiAgentEnv(ABC):
         field_of_view(agent, fov) [& line_of_sight(agent, obstacle)])` bit for bit, in the same launch
         (torch.ops.dgppo.lidar_observe_fov).  The beams stay omnidirectional.  None and 180 take exactly the paths
         without it."""
-        from ..utils.sensor import LidarNoise
+        from ..utils.sensor import Sensing, drop_below
 
         what = "observe"
-        self._require_lidar(what)
-        fov = self._fov_angle(what, fov)
+        sensing = Sensing.of(self, what, sigma, dropout, occlusion, fov)  # checks the env and all four options
+        sigma, dropout, fov = sensing.sigma, sensing.dropout, sensing.fov
         sense_range = float(self._params["comm_radius"])
-        model = LidarNoise(sigma, dropout, 0, sense_range=sense_range)  # checks sigma and dropout; Phi^-1(dropout)
         t, env_offset = int(t), int(env_offset)
         if t < 0 or env_offset < 0:
             raise ValueError(f"observe: t and env_offset must be >= 0, got {t} and {env_offset}")
@@ -626,6 +609,7 @@ class MultiAgentEnv(ABC):
         if g.states.dim() != 3 or g.states.shape[0] != B:
             raise ValueError(f"observe: out must hold {B} graphs")
         if self.cfg.variant != _lib.DGPPO_VARIANT_NONE:
+            model = sensing.model(sense_range)
             if not occlusion:
                 return self._observe_chained(model, agent, goal, third, t, seed, env_offset, g)
             from ..utils.sensor import mask_unseen
@@ -633,13 +617,13 @@ class MultiAgentEnv(ABC):
             visible = self.line_of_sight(agent, third)  # before the graph is written: `out` may alias the state
             return mask_unseen(self._observe_chained(model, agent, goal, third, t, seed, env_offset, g), visible)
         iseed = 0 if tkey is not None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        flags = (_lib.OBSERVE_NOISE if model.sigma > 0.0 else 0) | (_lib.OBSERVE_DROPOUT if model.dropout > 0.0 else 0)
+        flags = (_lib.OBSERVE_NOISE if sigma > 0.0 else 0) | (_lib.OBSERVE_DROPOUT if dropout > 0.0 else 0)
         op = torch.ops.dgppo.lidar_observe
         if occlusion:
             op, flags = torch.ops.dgppo.lidar_observe_los, flags | _lib.OBSERVE_SIGHT
         head = (self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
-                iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t, model.sigma / sense_range,
-                model._drop_below)
+                iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t, sigma / sense_range,
+                drop_below(dropout))
         if fov is not None:  # the heading envs have no variant: always the fused kernel
             torch.ops.dgppo.lidar_observe_fov(*head, flags | _lib.OBSERVE_FOV, fov, g.nodes, g.edges, g.states,
                                               g.receivers, g.senders)

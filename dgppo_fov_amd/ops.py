@@ -84,6 +84,11 @@ def _stream(t: Tensor) -> int:
     return _lib.stream_handle(t.device)
 
 
+def _returns_none(*args, **kwargs) -> None:
+    """The fake of every op here that only writes into its arguments."""
+    return None
+
+
 # ---- env -------------------------------------------------------------------------------------------
 @torch.library.custom_op("dgppo::env_step", mutates_args=("nodes", "edges", "out_states", "receivers", "senders",
                                                            "reward", "cost"))
@@ -112,10 +117,7 @@ def env_step(cfg: int, states: Tensor, obstacles: Optional[Tensor], action: Tens
                "dgppo_env_step")
 
 
-@env_step.register_fake
-def _env_step_fake(cfg, states, obstacles, action, ray_dirs, nodes, edges, out_states, receivers, senders, reward,
-                   cost) -> None:
-    return None
+env_step.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::env_reset", mutates_args=("obstacles", "nodes", "edges", "out_states", "receivers",
@@ -131,10 +133,7 @@ def env_reset(cfg: int, key: Optional[Tensor], seed: int, env_offset: int, n_env
                "dgppo_env_reset")
 
 
-@env_reset.register_fake
-def _env_reset_fake(cfg, key, seed, env_offset, n_env, obstacles, ray_dirs, nodes, edges, out_states, receivers,
-                    senders) -> None:
-    return None
+env_reset.register_fake(_returns_none)
 
 
 def _reset_io(key, seed, env_offset, n_env, obstacles, ray_dirs, nodes, edges, out_states, receivers, senders):
@@ -171,10 +170,7 @@ def env_reset_states(cfg: int, key: Optional[Tensor], seed: int, env_offset: int
                "dgppo_env_reset_states")
 
 
-@env_reset_states.register_fake
-def _env_reset_states_fake(cfg, key, seed, env_offset, n_env, obstacles, ray_dirs, nodes, edges, out_states,
-                           receivers, senders) -> None:
-    return None
+env_reset_states.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::env_rollout", mutates_args=("obstacles", "nodes", "edges", "states", "receivers",
@@ -246,10 +242,7 @@ def env_rollout_plan(cfg: int, rebuild_first: bool, obstacles: Optional[Tensor],
     return pl
 
 
-@env_rollout.register_fake
-def _env_rollout_fake(cfg, rebuild_first, obstacles, actions, ray_dirs, nodes, edges, states, receivers, senders,
-                      reward, cost, reset_first=False, key=None, seed=0, env_offset=0) -> None:
-    return None
+env_rollout.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::env_get_graph", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
@@ -274,9 +267,7 @@ def env_get_graph(cfg: int, agent: Tensor, goal: Tensor, third: Optional[Tensor]
                "dgppo_env_get_graph")
 
 
-@env_get_graph.register_fake
-def _env_get_graph_fake(cfg, agent, goal, third, ray_dirs, nodes, edges, states, receivers, senders) -> None:
-    return None
+env_get_graph.register_fake(_returns_none)
 
 
 # ---- sensor in the loop: scan | hits | graph from hits ---------------------------------------------------
@@ -296,9 +287,7 @@ def lidar_scan(cfg: int, agent: Tensor, obstacles: Tensor, ray_dirs: Tensor, alp
                "dgppo_lidar_scan")
 
 
-@lidar_scan.register_fake
-def _lidar_scan_fake(cfg, agent, obstacles, ray_dirs, alpha) -> None:
-    return None
+lidar_scan.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::lidar_hits", mutates_args=("hits",))
@@ -316,9 +305,7 @@ def lidar_hits(cfg: int, agent: Tensor, alpha: Tensor, ray_dirs: Tensor, hits: T
                "dgppo_lidar_hits")
 
 
-@lidar_hits.register_fake
-def _lidar_hits_fake(cfg, agent, alpha, ray_dirs, hits) -> None:
-    return None
+lidar_hits.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::env_get_graph_hits", mutates_args=("nodes", "edges", "states", "receivers",
@@ -342,9 +329,7 @@ def env_get_graph_hits(cfg: int, agent: Tensor, goal: Tensor, hits: Tensor, node
                "dgppo_env_get_graph_hits")
 
 
-@env_get_graph_hits.register_fake
-def _env_get_graph_hits_fake(cfg, agent, goal, hits, nodes, edges, states, receivers, senders) -> None:
-    return None
+env_get_graph_hits.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::lidar_observe", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
@@ -356,16 +341,15 @@ def lidar_observe(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_
     Phi^-1(dropout)), lidar_hits and env_get_graph_hits fused.  The draws of beam (b, i, r) are the Philox normals of
     element ((env_offset + b) n + i) R + r under (seed or *key) and the streams of step t.  `key`: optional 1-element
     int64 device tensor read at run time (hipGraph replays)."""
-    _lib.require_gpu(states.device, "dgppo::lidar_observe")
-    io = _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
-                     edges, states, receivers, senders)
-    _lib.check(_lib.load().dgppo_lidar_observe(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
-               "dgppo_lidar_observe")
+    _observe("lidar_observe", cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
+             flags, nodes, edges, states, receivers, senders)
 
 
-def _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
-                edges, states, receivers, senders) -> _lib.LidarObserveIO:
-    """The dgppo_lidar_observe_io of lidar_observe's / lidar_observe_los's arguments."""
+def _observe(name, cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
+             edges, states, receivers, senders, *extra) -> None:
+    """The body of the three observe ops: the dgppo_lidar_observe_io of their arguments, then the entry dgppo_<name>
+    (`extra`: what that entry takes between the io and the stream)."""
+    _lib.require_gpu(states.device, "dgppo::" + name)
     io = _lib.LidarObserveIO()
     io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
     io.goal, io.goal_stride = _p(goal), _stride(goal, 2)
@@ -385,13 +369,11 @@ def _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, nois
     else:
         io.seed, io.seed_ptr = int(seed) & 0xFFFFFFFFFFFFFFFF, None
     io.noise_scale, io.drop_below = float(noise_scale), float(drop_below)
-    return io
+    entry = getattr(_lib.load(), "dgppo_" + name)
+    _lib.check(entry(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), *extra, _stream(states)), "dgppo_" + name)
 
 
-@lidar_observe.register_fake
-def _lidar_observe_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
-                        flags, nodes, edges, states, receivers, senders) -> None:
-    return None
+lidar_observe.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::lidar_observe_los", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
@@ -401,17 +383,11 @@ def lidar_observe_los(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, 
                       senders: Tensor) -> None:
     """lidar_observe that also takes OBSERVE_SIGHT in `flags`: the observed graph with every agent-agent edge whose
     receiver cannot see its sender past the obstacles (lidar_sight) routed to the pad node, in the same launch."""
-    _lib.require_gpu(states.device, "dgppo::lidar_observe_los")
-    io = _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
-                     edges, states, receivers, senders)
-    _lib.check(_lib.load().dgppo_lidar_observe_los(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(states)),
-               "dgppo_lidar_observe_los")
+    _observe("lidar_observe_los", cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale,
+             drop_below, flags, nodes, edges, states, receivers, senders)
 
 
-@lidar_observe_los.register_fake
-def _lidar_observe_los_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
-                            flags, nodes, edges, states, receivers, senders) -> None:
-    return None
+lidar_observe_los.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::lidar_sight", mutates_args=("visible",))
@@ -431,9 +407,7 @@ def lidar_sight(cfg: int, agent: Tensor, obstacles: Tensor, visible: Tensor) -> 
                "dgppo_lidar_sight")
 
 
-@lidar_sight.register_fake
-def _lidar_sight_fake(cfg, agent, obstacles, visible) -> None:
-    return None
+lidar_sight.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::lidar_observe_fov", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
@@ -443,18 +417,11 @@ def lidar_observe_fov(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, 
                       receivers: Tensor, senders: Tensor) -> None:
     """lidar_observe_los that also takes OBSERVE_FOV in `flags`: every agent-agent edge whose sender is outside the
     receiver's forward cone of `half_angle_deg` (agent_fov) goes to the pad node as well, in the same launch."""
-    _lib.require_gpu(states.device, "dgppo::lidar_observe_fov")
-    io = _observe_io(agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below, flags, nodes,
-                     edges, states, receivers, senders)
-    _lib.check(_lib.load().dgppo_lidar_observe_fov(ctypes.byref(env_cfg(cfg)), ctypes.byref(io),
-                                                   float(half_angle_deg), _stream(states)),
-               "dgppo_lidar_observe_fov")
+    _observe("lidar_observe_fov", cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale,
+             drop_below, flags, nodes, edges, states, receivers, senders, float(half_angle_deg))
 
 
-@lidar_observe_fov.register_fake
-def _lidar_observe_fov_fake(cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale, drop_below,
-                            flags, half_angle_deg, nodes, edges, states, receivers, senders) -> None:
-    return None
+lidar_observe_fov.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::agent_fov", mutates_args=("in_fov",))
@@ -473,9 +440,7 @@ def agent_fov(cfg: int, agent: Tensor, half_angle_deg: float, in_fov: Tensor) ->
                "dgppo_agent_fov")
 
 
-@agent_fov.register_fake
-def _agent_fov_fake(cfg, agent, half_angle_deg, in_fov) -> None:
-    return None
+agent_fov.register_fake(_returns_none)
 
 
 def _render_args(states: Tensor, receivers: Tensor, senders: Tensor, obstacles: Optional[Tensor], out: Tensor,
@@ -526,9 +491,7 @@ def render_frames(cfg: int, states: Tensor, receivers: Tensor, senders: Tensor, 
                "dgppo_render_frames")
 
 
-@render_frames.register_fake
-def _render_frames_fake(cfg, states, receivers, senders, obstacles, out, flags) -> None:
-    return None
+render_frames.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::render_frames_field", mutates_args=("out",))
@@ -564,10 +527,7 @@ def render_frames_field(cfg: int, states: Tensor, receivers: Tensor, senders: Te
                                                      _stream(states)), "dgppo_render_frames_field")
 
 
-@render_frames_field.register_fake
-def _render_frames_field_fake(cfg, states, receivers, senders, obstacles, values, palette, extent, half_range, alpha,
-                              line_halfwidth, out, flags) -> None:
-    return None
+render_frames_field.register_fake(_returns_none)
 
 
 # ---- GraphTransformer attention core -------------------------------------------------------------------
@@ -603,10 +563,7 @@ def gnn_attn_fwd(dims: List[int], cand: Tensor, receivers: Tensor, senders: Tens
     _lib.check(_lib.load().dgppo_gnn_attn_fwd(ctypes.byref(a), _stream(qt)), "dgppo_gnn_attn_fwd")
 
 
-@gnn_attn_fwd.register_fake
-def _gnn_attn_fwd_fake(dims, cand, receivers, senders, sidx, x, x_gstride, ef, ef_gstride, q, qt, bk, scale, xa,
-                       xa_gstride, pre_W, pre_b, attn, xcat, beta=None, beta_ld=0, qt_ld=0) -> None:
-    return None
+gnn_attn_fwd.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::gnn_attn_bwd", mutates_args=("dqt", "dq", "dbeta", "dxa", "dpre_part", "dx"))
@@ -634,11 +591,7 @@ def gnn_attn_bwd(dims: List[int], cand: Tensor, receivers: Tensor, senders: Tens
     _lib.check(_lib.load().dgppo_gnn_attn_bwd(ctypes.byref(a), _stream(qt)), "dgppo_gnn_attn_bwd")
 
 
-@gnn_attn_bwd.register_fake
-def _gnn_attn_bwd_fake(dims, cand, receivers, senders, sidx, x, x_gstride, ef, ef_gstride, q, qt, bk, scale, xa,
-                       xa_gstride, pre_W, pre_b, attn, dxcat, da_add, dqt, dq, dbeta, dxa, dxa_gstride, dpre_part,
-                       beta=None, beta_ld=0, qt_ld=0, dqt_ld=0, dbeta_ld=0, dx=None, dx_gstride=0) -> None:
-    return None
+gnn_attn_bwd.register_fake(_returns_none)
 
 
 def gnn_attn_partial_blocks(dims, cand, receivers, senders, sidx, x, x_gstride, ef, ef_gstride, q, qt, bk, scale, xa,
@@ -706,10 +659,7 @@ def gnn_layer_fwd(dims: List[int], cand: Tensor, receivers: Tensor, senders: Ten
     _lib.check(_lib.load().dgppo_gnn_layer_fwd(ctypes.byref(la), _lib.stream_handle(dev)), "dgppo_gnn_layer_fwd")
 
 
-@gnn_layer_fwd.register_fake
-def _gnn_layer_fwd_fake(dims, cand, receivers, senders, sidx, x, x_gstride, ef, ef_gstride, scale, xa, xa_gstride,
-                        pre_W, pre_b, QBW, Wcat, Wu, bu, Y, qb, attn, xcat, zmean, tail_w, tail_h, tail_out) -> None:
-    return None
+gnn_layer_fwd.register_fake(_returns_none)
 
 
 # ---- GAE, clip + Adam ------------------------------------------------------------------------------------
@@ -730,9 +680,7 @@ def gae(hs: Tensor, l: Tensor, Vh: Tensor, Vl: Tensor, Qh: Tensor, Ql: Tensor, g
     _lib.check(_lib.load().dgppo_gae(ctypes.byref(a), _stream(hs)), "dgppo_gae")
 
 
-@gae.register_fake
-def _gae_fake(hs, l, Vh, Vl, Qh, Ql, gamma, lam) -> None:
-    return None
+gae.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::grad_norm", mutates_args=("state",))
@@ -746,9 +694,7 @@ def grad_norm(grad: Tensor, state: Tensor) -> None:
     _lib.check(lib.dgppo_grad_norm(_p(grad), int(grad.numel()), _p(state), _p(ws), _stream(grad)), "dgppo_grad_norm")
 
 
-@grad_norm.register_fake
-def _grad_norm_fake(grad, state) -> None:
-    return None
+grad_norm.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::adam", mutates_args=("param", "m", "v", "state"))
@@ -761,9 +707,7 @@ def adam(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, state: Tensor, lr: f
                                       float(b1), float(b2), float(eps), float(max_norm), _stream(param)), "dgppo_adam")
 
 
-@adam.register_fake
-def _adam_fake(param, grad, m, v, state, lr, b1, b2, eps, max_norm) -> None:
-    return None
+adam.register_fake(_returns_none)
 
 
 # ---- minibatch assembly ---------------------------------------------------------------------------------
@@ -797,6 +741,4 @@ def gather_env_steps(src: List[Tensor], dst: List[Tensor], envs: Tensor) -> None
                "dgppo_gather_env_steps")
 
 
-@gather_env_steps.register_fake
-def _gather_env_steps_fake(src, dst, envs) -> None:
-    return None
+gather_env_steps.register_fake(_returns_none)

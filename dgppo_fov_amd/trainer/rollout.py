@@ -24,7 +24,7 @@ from ..env.base import MultiAgentEnv
 from ..nn import kernels as K
 from ..nn.layers import GraphBatch
 from ..utils.graph import GraphsTuple
-from ..utils.sensor import mask_unseen
+from ..utils.sensor import Sensing, mask_unseen
 from .data import Rollout
 
 
@@ -249,7 +249,58 @@ class RolloutEngine:
                        self.costs.transpose(0, 1), self.dones.transpose(0, 1), log_pis, view(slice(1, T + 1)))
 
 
-class SensorRolloutEngine(RolloutEngine):
+class _ObservedRolloutEngine(RolloutEngine):
+    """What the two sensor engines share: per step the actor acts on an OBSERVED graph, kept in the time-major buffer
+    `obs`, while env.step_into advances the TRUE graph in `buf` and writes the true reward and cost.  `sensing` is the
+    utils.sensor.Sensing record the engine was built from or for (None: nothing beyond the subclass's own sensor); its
+    `occlusion` and `fov` are attributes here.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env with
+    obstacles."""
+
+    @staticmethod
+    def _need_actor(what: str, actor, mode: int) -> None:
+        if actor is None or mode not in (RolloutEngine.MODE_DET, RolloutEngine.MODE_SAMPLE):
+            raise ValueError(f"{what}: needs an actor in MODE_DET or MODE_SAMPLE")
+
+    def __init__(self, what: str, sensing: Optional[Sensing], final_obs: bool, env: MultiAgentEnv, n_env: int, T, device,
+                 env_offset: int, actor, mode: int, init_state):
+        env._require_lidar(what)
+        super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
+        self.sensing = sensing
+        self.occlusion, self.fov = (sensing.occlusion, sensing.fov) if sensing is not None else (False, None)
+        # time-major, like buf; with final_obs one more graph, observed from the final true state
+        self.obs = env.empty_graph((self.T + int(final_obs), self.B), self.device)
+
+    def _observed_at(self, t: int) -> GraphsTuple:
+        b = self.obs
+        return self.env._assemble(b.nodes[t], b.edges[t], b.states[t], b.receivers[t], b.senders[t], self.obstacles)
+
+    def _batch(self, t: int, sl=slice(None)) -> GraphBatch:  # the actor's input: the observed graph of step t
+        b = self.obs
+        return GraphBatch.of(self.env, b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl])
+
+    def _run(self):
+        env = self.env
+        if self.init_state is not None:
+            cur = env.get_graph(self.init_state, out=self.graph_at(0))
+        else:
+            cur = env.reset(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
+                            obstacles_out=self.obstacles)
+        for t in range(self.T):
+            self._observe(t)
+            self._act(t)
+            cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
+
+    @property
+    def observed(self) -> GraphsTuple:
+        """The graphs the actor saw (and with them the final one where the engine observes it), batch shape (B, T) or
+        (B, T + 1): views of the time-major buffer."""
+        b = self.obs
+        tr = lambda x: x.transpose(0, 1)  # noqa: E731
+        return self.env._assemble(tr(b.nodes), tr(b.edges), tr(b.states), tr(b.receivers), tr(b.senders),
+                                  self.obstacles)
+
+
+class SensorRolloutEngine(_ObservedRolloutEngine):
     """RolloutEngine with a LiDAR sensor model between the world and the policy.
 
     Per step t: alpha = env.lidar_scan(agent_t, obstacles); alpha_obs = sensor(alpha, t); the OBSERVED graph is
@@ -263,67 +314,43 @@ class SensorRolloutEngine(RolloutEngine):
     each other -- each observed graph then goes through utils.sensor.mask_unseen with env.line_of_sight of the true
     state, and `sensor` may be None (the identity).  fov: a half angle in degrees (the envs with a heading) -- the
     senders outside the receiver's camera cone are hidden too (env.field_of_view, ANDed into the same mask); None and
-    180 mean no cone, and `sensor` may be None here as well.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env
-    with obstacles; no hipGraph capture (a sensor is arbitrary Python)."""
+    180 mean no cone, and `sensor` may be None here as well.  sensing: a utils.sensor.Sensing in place of occlusion and
+    fov, and of `sensor` when that is None (the record's LidarNoise, seed 0).  No hipGraph capture (a sensor is
+    arbitrary Python)."""
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_DET, sensor=None, init_state=None,
-                 occlusion: bool = False, fov=None):
-        fov = env._fov_angle("SensorRolloutEngine", fov)
-        if sensor is None and (occlusion or fov is not None):
-            sensor = lambda alpha, t: alpha  # noqa: E731
+                 occlusion: bool = False, fov=None, sensing: Optional[Sensing] = None):
+        what = "SensorRolloutEngine"
+        if sensing is None:
+            sensing = Sensing.of(env, what, occlusion=occlusion, fov=fov)
+        if sensor is None and sensing is not None:
+            sensor = sensing.model(float(env.params["comm_radius"]))
         if not callable(sensor):
             raise ValueError("SensorRolloutEngine: sensor must be a callable (alpha, t) -> alpha_obs")
-        if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
-            raise ValueError("SensorRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
-        env._require_lidar("SensorRolloutEngine")
-        super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
-        self.sensor, self.occlusion, self.fov = sensor, bool(occlusion), fov
-        self.obs_buf = env.empty_graph((self.T, self.B), self.device)  # time-major, like buf
+        self._need_actor(what, actor, mode)
+        super().__init__(what, sensing, False, env, n_env, T, device, env_offset, actor, mode, init_state)
+        self.sensor = sensor
 
-    def _observed_at(self, t: int) -> GraphsTuple:
-        b = self.obs_buf
-        return self.env._assemble(b.nodes[t], b.edges[t], b.states[t], b.receivers[t], b.senders[t], self.obstacles)
-
-    def _batch(self, t: int, sl=slice(None)) -> GraphBatch:  # the actor's input: the observed graph of step t
-        b = self.obs_buf
-        return GraphBatch.of(self.env, b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl])
-
-    def _run(self):
+    def _observe(self, t: int):
         env, n = self.env, self.env.num_agents
-        if self.init_state is not None:
-            cur = env.get_graph(self.init_state, out=self.graph_at(0))
-        else:
-            cur = env.reset(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
-                            obstacles_out=self.obstacles)
-        for t in range(self.T):
-            agent = self.buf.states[t][:, :n]
-            goal = self.buf.states[t][:, n:n + env.num_goals]
-            alpha_obs = self.sensor(env.lidar_scan(agent, self.obstacles), t)
-            seen = env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
-                                 lidar_data=env.lidar_hits(agent, alpha_obs))
-            if self.occlusion or self.fov is not None:
-                vis = env.line_of_sight(agent, self.obstacles) if self.occlusion else None
-                if self.fov is not None:
-                    cone = env.field_of_view(agent, self.fov)
-                    vis = cone if vis is None else vis & cone
-                mask_unseen(seen, vis)
-            self._act(t)
-            cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
+        agent = self.buf.states[t][:, :n]
+        goal = self.buf.states[t][:, n:n + env.num_goals]
+        alpha_obs = self.sensor(env.lidar_scan(agent, self.obstacles), t)
+        seen = env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
+                             lidar_data=env.lidar_hits(agent, alpha_obs))
+        if self.occlusion or self.fov is not None:
+            vis = env.line_of_sight(agent, self.obstacles) if self.occlusion else None
+            if self.fov is not None:
+                cone = env.field_of_view(agent, self.fov)
+                vis = cone if vis is None else vis & cone
+            mask_unseen(seen, vis)
 
     def capture(self):
         raise NotImplementedError("SensorRolloutEngine: hipGraph capture of the sensor loop is not built")
 
-    @property
-    def observed(self) -> GraphsTuple:
-        """The graphs the actor saw, batch shape (B, T): (B, T, ...) views of the time-major buffer."""
-        b = self.obs_buf
-        tr = lambda x: x.transpose(0, 1)  # noqa: E731
-        return self.env._assemble(tr(b.nodes), tr(b.edges), tr(b.states), tr(b.receivers), tr(b.senders),
-                                  self.obstacles)
 
-
-class NoisyLidarRolloutEngine(RolloutEngine):
+class NoisyLidarRolloutEngine(_ObservedRolloutEngine):
     """RolloutEngine under the LidarNoise sensor model (utils/sensor.py), the sensor one fused launch per step
     (env.observe, torch.ops.dgppo.lidar_observe), so the whole rollout captures into a hipGraph: what training under
     the sensor model runs.  SensorRolloutEngine(sensor=LidarNoise(sigma, dropout, seed=key)) is its definition; this
@@ -336,33 +363,21 @@ class NoisyLidarRolloutEngine(RolloutEngine):
     with the policy's (env_offset << 32) | t while env_offset < 2^30 (check_env_offset refuses more); env b's beams
     draw at row env_offset + b.  occlusion: env.observe(..., occlusion=True), the agents hidden from each other by
     obstacles dropped from every observed graph in the same launch.  fov: env.observe(..., fov=deg), the senders outside
-    the receiver's camera cone dropped as well (the envs with a heading; None and 180: no cone).
+    the receiver's camera cone dropped as well (the envs with a heading; None and 180: no cone).  sensing: a
+    utils.sensor.Sensing in place of the four keywords.
 
     `run` returns the true Rollout; `observed_rollout()` the Rollout the algorithms train on: graph and next_graph
-    the observed ones, every other field the true run's.  MODE_DET or MODE_SAMPLE with an actor, one lane, a Lidar env
-    with obstacles."""
+    the observed ones, every other field the true run's."""
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_SAMPLE, sigma: float = 0.0, dropout: float = 0.0,
-                 init_state=None, occlusion: bool = False, fov=None):
-        from ..utils.sensor import LidarNoise
-
-        if actor is None or mode not in (self.MODE_DET, self.MODE_SAMPLE):
-            raise ValueError("NoisyLidarRolloutEngine: needs an actor in MODE_DET or MODE_SAMPLE")
-        env._require_lidar("NoisyLidarRolloutEngine")
-        model = LidarNoise(sigma, dropout, 0, sense_range=float(env.params["comm_radius"]))  # checks both
-        self.sigma, self.dropout, self.occlusion = model.sigma, model.dropout, bool(occlusion)
-        self.fov = env._fov_angle("NoisyLidarRolloutEngine", fov)
-        super().__init__(env, n_env, T, device, env_offset, actor, mode, lanes=1, init_state=init_state)
-        self.obs = env.empty_graph((self.T + 1, self.B), self.device)  # time-major, like buf
-
-    def _observed_at(self, t: int) -> GraphsTuple:
-        b = self.obs
-        return self.env._assemble(b.nodes[t], b.edges[t], b.states[t], b.receivers[t], b.senders[t], self.obstacles)
-
-    def _batch(self, t: int, sl=slice(None)) -> GraphBatch:  # the actor's input: the observed graph of step t
-        b = self.obs
-        return GraphBatch.of(self.env, b.nodes[t][sl], b.edges[t][sl], b.receivers[t][sl], b.senders[t][sl])
+                 init_state=None, occlusion: bool = False, fov=None, sensing: Optional[Sensing] = None):
+        what = "NoisyLidarRolloutEngine"
+        self._need_actor(what, actor, mode)
+        if sensing is None:
+            sensing = Sensing.of(env, what, sigma, dropout, occlusion, fov)
+        super().__init__(what, sensing, True, env, n_env, T, device, env_offset, actor, mode, init_state)
+        self.sigma, self.dropout = sensing.sigma or 0.0, sensing.dropout or 0.0
 
     def _observe(self, t: int):
         env, n = self.env, self.env.num_agents
@@ -372,25 +387,8 @@ class NoisyLidarRolloutEngine(RolloutEngine):
                     fov=self.fov)
 
     def _run(self):
-        env = self.env
-        if self.init_state is not None:
-            cur = env.get_graph(self.init_state, out=self.graph_at(0))
-        else:
-            cur = env.reset(self.key, n_env=self.B, env_offset=self.env_offset, out=self.graph_at(0),
-                            obstacles_out=self.obstacles)
-        for t in range(self.T):
-            self._observe(t)
-            self._act(t)
-            cur = env.step_into(cur, self.actions[t], self.graph_at(t + 1), self.rewards[t], self.costs[t])
+        super()._run()
         self._observe(self.T)
-
-    @property
-    def observed(self) -> GraphsTuple:
-        """The T + 1 observed graphs, batch shape (B, T + 1): views of the time-major buffer."""
-        b = self.obs
-        tr = lambda x: x.transpose(0, 1)  # noqa: E731
-        return self.env._assemble(tr(b.nodes), tr(b.edges), tr(b.states), tr(b.receivers), tr(b.senders),
-                                  self.obstacles)
 
     def observed_rollout(self) -> Rollout:
         """The last run as the algorithms read it: graph = obs[0:T] and next_graph = obs[1:T+1] as (B, T) views,

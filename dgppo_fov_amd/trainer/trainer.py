@@ -67,16 +67,11 @@ class Trainer:
         """test_rollout with the deterministic policy on n_env_test envs (trainer.py:85-116)."""
         assert self.n_env_test <= 1_000, "n_env_test must be less than or equal to 1_000"
         if self._test_engine is None:
-            sensor = getattr(self.algo, "sensor", None)
-            occlusion = bool(getattr(self.algo, "occlusion", False))
-            fov = getattr(self.algo, "fov", None)
-            # trained under a sensor model: the true costs under sensed control
-            if sensor is not None or occlusion or fov is not None:
-                sigma, dropout = sensor or (0.0, 0.0)
+            sensing = getattr(self.algo, "sensing", None)
+            if sensing is not None:  # trained under a sensor model: the true costs under sensed control
                 self._test_engine = NoisyLidarRolloutEngine(
                     self.env_test, self.n_env_test, self.env_test.max_episode_steps, self.algo.device,
-                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sigma=sigma, dropout=dropout,
-                    occlusion=occlusion, fov=fov)
+                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sensing=sensing)
             else:
                 self._test_engine = RolloutEngine(self.env_test, self.n_env_test, self.env_test.max_episode_steps,
                                                   self.algo.device, actor=self.algo.actor, mode=RolloutEngine.MODE_DET)

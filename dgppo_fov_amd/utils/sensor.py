@@ -13,6 +13,8 @@ agent-agent edges that an obstacle cuts (`env.observe(..., occlusion=True)` is t
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -54,6 +56,89 @@ def mask_unseen(graph, visible: torch.Tensor):
     return graph
 
 
+def noise_domain(sigma, dropout) -> None:
+    """LidarNoise's domain: sigma finite and >= 0, dropout in [0, 1], else ValueError."""
+    if not (math.isfinite(sigma) and sigma >= 0):
+        raise ValueError(f"LidarNoise: sigma must be >= 0, got {sigma}")
+    if not 0.0 <= dropout <= 1.0:
+        raise ValueError(f"LidarNoise: dropout must be in [0, 1], got {dropout}")
+
+
+def drop_below(dropout: float) -> float:
+    """Phi^-1(dropout) = sqrt(2) erfinv(2 dropout - 1): a beam is dropped where its standard normal draw is below it."""
+    if dropout <= 0.0:
+        return -math.inf
+    if dropout >= 1.0:
+        return math.inf
+    return math.sqrt(2.0) * float(torch.erfinv(torch.tensor(2.0 * dropout - 1.0, dtype=torch.float64)))
+
+
+def cone_angle(env, what: str, fov) -> Optional[float]:
+    """The half angle of a sensing cone in degrees, or None for no cone (`fov` None or exactly 180).  A cone needs an
+    env whose state carries a heading (LidarBicycleTarget, LidarOmniTarget) and 0 < fov <= 180: ValueError otherwise
+    (NotImplementedError for the VMAS envs), before the GPU is touched."""
+    if fov is None:
+        return None
+    if env.ENGINE in env._VMAS_ENGINES:
+        raise NotImplementedError(f"{what}: the VMAS envs have no field-of-view sensor model")
+    if env.ENGINE not in (_lib.DGPPO_ENGINE_BICYCLE, _lib.DGPPO_ENGINE_OMNI):
+        raise ValueError(f"{what}: a field of view needs a heading in the state (LidarBicycleTarget, "
+                         f"LidarOmniTarget); {type(env).__name__} has no heading")
+    deg = float(fov)
+    if not 0.0 < deg <= 180.0:
+        raise ValueError(f"{what}: the half angle must be in (0, 180] degrees, got {fov}")
+    return None if deg == 180.0 else deg
+
+
+@dataclass(frozen=True)
+class Sensing:
+    """What stands between the world and the policy, validated once: range noise `sigma` (world units) and beam
+    `dropout` (LidarNoise; both None when no noise value was given, which is not the same as 0: the algorithms report
+    it as `sensor is None`), `occlusion` (obstacles hide agents from each other) and `fov` (the half angle in degrees
+    of the camera cone, None for no cone).  make_algo, Trainer.evaluate, both sensor rollout engines, env.observe and
+    test.py all get theirs from `Sensing.of`."""
+
+    sigma: Optional[float]
+    dropout: Optional[float]
+    occlusion: bool
+    fov: Optional[float]
+
+    @classmethod
+    def of(cls, env, what: str, noise=None, dropout=None, occlusion=False, fov=None, algo_cls=None) -> Optional["Sensing"]:
+        """The record for these options on `env`, or None when nothing is sensed (no noise value given, no occlusion,
+        `fov` None or exactly 180).  `what` prefixes the messages.  The checks, in order: an algorithm (`algo_cls`)
+        that reads the true state off the rollout's graphs (SENSOR_OK False) takes no option at all, and one that can
+        needs a LiDAR env (its own wording); noise values are checked where they are given, first that the env has a
+        LiDAR, then LidarNoise's domain; then the cone (cone_angle); then, if not yet done, that the env has a LiDAR.
+        ValueError, or NotImplementedError for the VMAS envs, before the GPU is touched."""
+        if noise is None and dropout is None and not occlusion and fov is None:
+            return None
+        no_lidar = env._obstacle_fields() == 0 or env.n_obs == 0
+        if algo_cls is not None:
+            flags = "lidar_noise / lidar_dropout / lidar_occlusion / lidar_fov"
+            if not algo_cls.SENSOR_OK:
+                raise ValueError(f"{algo_cls.__name__} evaluates env.get_cost on the rollout's graphs, which must be "
+                                 f"the true ones: {flags} are not supported (dgppo, informarl, informarl_lagr are)")
+            if env.ENGINE in env._VMAS_ENGINES or no_lidar:
+                raise ValueError(f"{flags} need a LiDAR env with obstacles; {type(env).__name__} with {env.n_obs} "
+                                 "obstacles has no LiDAR")
+        sigma = drop = None
+        if noise is not None or dropout is not None:
+            env._require_lidar(what)
+            noise_domain(noise or 0.0, dropout or 0.0)
+            sigma, drop = float(noise or 0.0), float(dropout or 0.0)
+        fov = cone_angle(env, what, fov)
+        if sigma is None and not occlusion and fov is None:
+            return None
+        if sigma is None:
+            env._require_lidar(what)
+        return cls(sigma, drop, bool(occlusion), fov)
+
+    def model(self, sense_range: float, seed: int = 0) -> "LidarNoise":
+        """The record's LidarNoise (sigma = dropout = 0, the identity, when no noise value was given)."""
+        return LidarNoise(self.sigma or 0.0, self.dropout or 0.0, seed, sense_range=sense_range)
+
+
 class LidarNoise:
     """Range noise and beam dropout: `LidarNoise(sigma, dropout, seed)(alpha, t)`.
 
@@ -70,20 +155,11 @@ class LidarNoise:
     STREAM_BASE = 1 << 62
 
     def __init__(self, sigma: float = 0.0, dropout: float = 0.0, seed: int = 0, sense_range: float = 0.5):
-        if not (math.isfinite(sigma) and sigma >= 0):
-            raise ValueError(f"LidarNoise: sigma must be >= 0, got {sigma}")
-        if not 0.0 <= dropout <= 1.0:
-            raise ValueError(f"LidarNoise: dropout must be in [0, 1], got {dropout}")
+        noise_domain(sigma, dropout)
         if not (math.isfinite(sense_range) and sense_range > 0):
             raise ValueError(f"LidarNoise: sense_range must be positive, got {sense_range}")
         self.sigma, self.dropout, self.seed, self.sense_range = float(sigma), float(dropout), int(seed), float(sense_range)
-        if self.dropout <= 0.0:
-            self._drop_below = -math.inf
-        elif self.dropout >= 1.0:
-            self._drop_below = math.inf
-        else:  # Phi^-1(p) = sqrt(2) erfinv(2p - 1)
-            self._drop_below = math.sqrt(2.0) * float(torch.erfinv(torch.tensor(2.0 * self.dropout - 1.0,
-                                                                                 dtype=torch.float64)))
+        self._drop_below = drop_below(self.dropout)
 
     def __call__(self, alpha: torch.Tensor, t: int) -> torch.Tensor:
         if self.sigma == 0.0 and self.dropout == 0.0:

@@ -75,14 +75,12 @@ def test(args):
     sensed = (args.lidar_noise is not None or args.lidar_dropout is not None or args.lidar_occlusion
               or args.lidar_fov is not None)
     if sensed:  # refused before anything is loaded or run
+        from dgppo_fov_amd.utils.sensor import Sensing
+
         sigma, drop = args.lidar_noise or 0.0, args.lidar_dropout or 0.0
-        if env._obstacle_fields() == 0 or env.n_obs == 0 or not hasattr(env, "lidar_scan"):
-            raise SystemExit("--lidar-noise / --lidar-dropout / --lidar-occlusion / --lidar-fov need a LiDAR env with "
-                             f"obstacles; {type(env).__name__} with {env.n_obs} obstacles has no LiDAR")
-        if not sigma >= 0.0 or not 0.0 <= drop <= 1.0:
-            raise SystemExit(f"--lidar-noise must be >= 0 and --lidar-dropout in [0, 1], got {sigma} and {drop}")
         try:
-            fov = env._fov_angle("--lidar-fov", args.lidar_fov)
+            sensing = Sensing.of(env, "--lidar-noise / --lidar-dropout / --lidar-occlusion / --lidar-fov", sigma, drop,
+                                 args.lidar_occlusion, args.lidar_fov)
         except (ValueError, NotImplementedError) as e:
             raise SystemExit(str(e))
     if args.cbf is not None and args.video and not args.no_video:  # refused before anything is loaded or run
@@ -119,12 +117,10 @@ def test(args):
         init_state = type(scene)(*(cut(part) for part in scene))
     if sensed:
         from dgppo_fov_amd.trainer.rollout import SensorRolloutEngine
-        from dgppo_fov_amd.utils.sensor import LidarNoise
 
-        sensor = LidarNoise(sigma, drop, args.seed, sense_range=float(env.params["comm_radius"]))
+        sensor = sensing.model(float(env.params["comm_radius"]), seed=args.seed)
         eng = SensorRolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset,
-                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state,
-                                  occlusion=args.lidar_occlusion, fov=fov)
+                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state, sensing=sensing)
     else:
         eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
                             mode=mode, init_state=init_state)

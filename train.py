@@ -59,8 +59,12 @@ def train(args):
         os.environ["CUDA_VISIBLE_DEVICES"] = str(args.gpu)
         print(f"> Using GPU: {args.gpu}")
     if args.lidar_noise is not None or args.lidar_dropout is not None:  # refused before the GPU is touched
+        from dgppo_fov_amd.utils.sensor import LidarNoise
+
         sigma, drop = args.lidar_noise or 0.0, args.lidar_dropout or 0.0
-        if not sigma >= 0.0 or not 0.0 <= drop <= 1.0:
+        try:  # the sensor model's own domain; what needs the env is refused by make_algo (utils.sensor.Sensing.of)
+            LidarNoise(sigma, drop)
+        except ValueError:
             raise SystemExit(f"--lidar-noise must be >= 0 and --lidar-dropout in [0, 1], got {sigma} and {drop}")
     import torch
     import torch.distributed as dist
