@@ -458,6 +458,7 @@ SIGNATURES = {
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),
                                                  ctypes.POINTER(RenderField), ctypes.c_void_p]),
+    "dgppo_render_frames_vmas": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_gemm_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs)]),
     "dgppo_gemm_wgrad_grouped_workspace_floats": (ctypes.c_int64, [ctypes.POINTER(GemmArgs), ctypes.c_int]),
     "dgppo_gemm_wgrad_grouped": (ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_int, c_f32p, ctypes.c_void_p]),

@@ -682,31 +682,18 @@ class MultiAgentEnv(ABC):
         viz_opts={"field": FieldLayer} (utils/field.py) draws a scalar field per frame -- hard-edged colour bands and a
         black zero line -- under every other layer (torch.ops.dgppo.render_frames_field): this project's door to the
         picture the reference draws for viz_opts["cbf"] / ["Vh"], keys that stay unbuilt here."""
-        if self.ENGINE in self._VMAS_ENGINES:
-            raise NotImplementedError(f"{type(self).__name__}: rendering the VMAS envs is not built (their reference "
-                                      "renderers are separate code)")
         viz_opts = viz_opts or {}
         for key in ("cbf", "Vh"):
             if key in viz_opts:
                 raise NotImplementedError(f"viz_opts[{key!r}] (the reference's contour overlay): not built")
         _lib.require_gpu(graph.states.device, "env.render_frames")
         states, recv, send = graph.states, graph.receivers, graph.senders
-        bs = tuple(states.shape[:-2])
-        if len(bs) not in (1, 2) or tuple(states.shape[-2:]) != (self.n_nodes, self.state_dim):
-            raise ValueError("render_frames: graph must have batch shape (B,) or (B, T) and this env's layout")
-        S = int(size) if size else 10 * int(dpi)
-        if S < 1:
-            raise ValueError(f"render_frames: image size must be >= 1, got {S}")
+        bs, out = self._frame_buffer(states, size, dpi, out)
         ob = self._obstacles_of(graph) if self._obstacle_fields() > 0 else None
         if ob is not None and len(bs) == 2:  # one obstacle set per episode: the (B, T) views expand it over T
             if ob.shape[1] > 1 and ob.stride(1) != 0:
                 raise ValueError("render_frames: a (B, T) graph needs one obstacle set per episode")
             ob = ob[:, 0]
-        shape = bs + (S, S, 4)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=states.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != states.device:
-            raise ValueError(f"render_frames: out must be a uint8 {shape} tensor on {states.device}")
         flags = _lib.RENDER_FOV if viz_opts.get("fov", True) else 0
         field = viz_opts.get("field")
         if field is None:
@@ -723,6 +710,21 @@ class MultiAgentEnv(ABC):
                                             palette_tensor(field.bands, states.device), list(field.extent),
                                             field.half_range, FIELD_ALPHA, self._area_size / 480.0, out, flags)
         return out
+
+    def _frame_buffer(self, states: torch.Tensor, size: Optional[int], dpi: int, out: Optional[torch.Tensor]):
+        """(batch shape, the uint8 (*batch, S, S, 4) image stack) of a render_frames call: `out`, checked, or new."""
+        bs = tuple(states.shape[:-2])
+        if len(bs) not in (1, 2) or tuple(states.shape[-2:]) != (self.n_nodes, self.state_dim):
+            raise ValueError("render_frames: graph must have batch shape (B,) or (B, T) and this env's layout")
+        S = int(size) if size else 10 * int(dpi)
+        if S < 1:
+            raise ValueError(f"render_frames: image size must be >= 1, got {S}")
+        shape = bs + (S, S, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=states.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != states.device:
+            raise ValueError(f"render_frames: out must be a uint8 {shape} tensor on {states.device}")
+        return bs, out
 
     def render_video(self, rollout, video_path, Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
                      episode: int = 0, max_frame_bytes: int = 1 << 30) -> str:
@@ -741,24 +743,19 @@ class MultiAgentEnv(ABC):
         except ImportError as e:
             raise ImportError("render_video needs Pillow for the text and the GIF; env.render_frames returns the "
                               "frames without it") from e
-        if self.ENGINE in self._VMAS_ENGINES:
-            raise NotImplementedError(f"{type(self).__name__}: rendering the VMAS envs is not built (their reference "
-                                      "renderers are separate code)")
         g = rollout.graph
         if g.states.dim() != 4 or g.states.shape[1] < 1:
             raise ValueError("render_video: rollout.graph must have batch shape (B, T) with T >= 1")
         T, n, S = int(g.states.shape[1]), self._num_agents, 10 * int(dpi)
         band = S // 8
         per = max(1, int(max_frame_bytes) // (S * S * 4))
-        ob = self._obstacles_of(g) if self._obstacle_fields() > 0 and self.ENGINE not in self._VMAS_ENGINES else None
+        ob = self._obstacles_of(g) if self._obstacle_fields() > 0 else None
         costs = rollout.costs[episode].amax(dim=1).double().cpu().numpy()  # (T, n_cost) max over agents
         rewards = rollout.rewards[episode].double().cpu().numpy()
         pos = g.states[episode, :, :n, :2].double().cpu().numpy()  # (T, n, 2)
         unsafe = None if Ta_is_unsafe is None else np.asarray(
             Ta_is_unsafe.cpu() if isinstance(Ta_is_unsafe, torch.Tensor) else Ta_is_unsafe).astype(bool)
-        names = self.cost_components
-        lines = 2 + len(names)
-        px = max(6, band // (lines + 1))
+        px = max(6, band // (self._header_line_count() + 1))
         frames, h = [], self._area_size / S
         lpx = max(px, int(1.4 * float(self._params.get("car_radius", 0.05)) / h))  # labels: about the agent's radius
         try:
@@ -766,6 +763,7 @@ class MultiAgentEnv(ABC):
         except (TypeError, OSError):  # a Pillow without the scalable default font
             font = label_font = ImageFont.load_default()
             lpx = px
+        host = self._header_host(g, episode)
         field = (viz_opts or {}).get("field")
         if field is not None and (not hasattr(field, "sliced") or tuple(field.values.shape[:-2]) != (T,)):
             raise ValueError(f"render_video: viz_opts['field'] must be a FieldLayer with values ({T}, Gy, Gx)")
@@ -781,16 +779,16 @@ class MultiAgentEnv(ABC):
                 im = Image.new("RGB", (S, S + band), "white")
                 im.paste(Image.fromarray(rgb[t - t0], "RGB"), (0, band))
                 d = ImageDraw.Draw(im)
-                text = "Cost:\n" + "\n".join(f"    {nm}: {costs[t, i]:5.4f}" for i, nm in enumerate(names))
-                d.multiline_text((S // 50, 0), text + f"\nReward: {rewards[t]:5.4f}", fill="black", font=font, spacing=0)
-                right = [f"kk={t:04}"]
+                left, right = self._header_text(host, t, costs[t], rewards[t])
+                if left:
+                    d.multiline_text((S // 50, 0), left, fill="black", font=font, spacing=0)
                 if unsafe is not None and t < len(unsafe):
-                    right.append("Unsafe: [" + " ".join(str(i) for i in np.where(unsafe[t])[0]) + "]")  # one line
+                    right = right + ["Unsafe: [" + " ".join(str(i) for i in np.where(unsafe[t])[0]) + "]"]  # one line
                 for i, s in enumerate(right):
                     d.text((S - S // 100 - d.textlength(s, font=font), i * px), s, fill="black", font=font)
                 if field is not None and field.label:
                     d.text(((S - d.textlength(field.label, font=font)) / 2, 0), field.label, fill="black", font=font)
-                for i in range(n):
+                for i in range(n if self._labels_agents else 0):
                     x, y = pos[t, i]
                     if np.isfinite(x) and np.isfinite(y) and 0 <= x <= self._area_size and 0 <= y <= self._area_size:
                         d.text((x / h - d.textlength(str(i), font=label_font) / 2, band + S - y / h - 0.6 * lpx), str(i),
@@ -802,6 +800,21 @@ class MultiAgentEnv(ABC):
         path.parent.mkdir(parents=True, exist_ok=True)
         frames[0].save(path, save_all=True, append_images=frames[1:], duration=1000 // 30, loop=0, optimize=False)
         return str(path)
+
+    _labels_agents = True  # render_video writes each agent's index at its centre
+
+    def _header_line_count(self) -> int:
+        """Text lines the header band of render_video has room for."""
+        return 2 + len(self.cost_components)
+
+    def _header_host(self, graph: GraphsTuple, episode: int):
+        """Host copies of what _header_text reads beyond costs and rewards (taken once per video)."""
+        return None
+
+    def _header_text(self, host, t: int, costs_t, reward_t):
+        """Frame t's header of render_video: (the left block, the right-aligned lines top to bottom)."""
+        left = "Cost:\n" + "\n".join(f"    {nm}: {costs_t[i]:5.4f}" for i, nm in enumerate(self.cost_components))
+        return left + f"\nReward: {reward_t:5.4f}", [f"kk={t:04}"]
 
     def get_cost(self, graph: GraphsTuple) -> torch.Tensor:
         """Cost of a graph (lidar_env/base.py:180-207): the step kernel evaluates it on its input."""

@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes
 from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 
 from ... import _lib
@@ -142,6 +143,63 @@ class VMASEnv(MultiAgentEnv):
             raise ValueError("VMAS env records must be contiguous per env")
         return rec
 
+    # ---- rendering (vmas_wheel.py:317-422, vmas_reverse_transport.py:322-431) ---------------------------------
+    _labels_agents = False  # the reference writes no agent index in these pictures
+
+    def render_frames(self, graph: GraphsTuple, size: Optional[int] = None, dpi: int = 100,
+                      viz_opts: Optional[dict] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The base method for the VMAS envs: the scene of every graph of `graph` (batch shape (B,) or (B, T)) as a
+        uint8 RGBA image (*batch, S, S, 4) on the graph's device, one HIP launch (torch.ops.dgppo.render_frames_vmas;
+        DESIGN.md "Rendering" has the view and the two layer tables).  The record is graph.env_states.record, one per
+        episode.  There is no host path, and no value sweep (get_graph of given states does not exist here), so
+        viz_opts keys field / cbf / Vh are refused; fov is ignored."""
+        viz_opts = viz_opts or {}
+        for key in ("field", "cbf", "Vh"):
+            if key in viz_opts:
+                raise NotImplementedError(f"{type(self).__name__}: viz_opts[{key!r}] is not built for the VMAS envs "
+                                          "(no get_graph of given states, so no value sweep)")
+        if graph.states.device.type != "cuda":
+            raise NotImplementedError(f"{type(self).__name__}: rendering the VMAS envs has no host path; the graph must "
+                                      "be on a GPU")
+        states = graph.states
+        bs, out = self._frame_buffer(states, size, dpi, out)
+        rec = self._obstacles_of(graph)
+        if len(bs) == 2:  # one record per episode: the (B, T) views expand it over T
+            if rec.shape[1] > 1 and rec.stride(1) != 0:
+                raise ValueError("render_frames: a (B, T) graph needs one env record per episode")
+            rec = rec[:, 0]
+        torch.ops.dgppo.render_frames_vmas(self._cfg_handle, states, rec, out)
+        return out
+
+    def _header_line_count(self) -> int:
+        return 5  # four lines of the reference and `Unsafe:`
+
+    def _header_host(self, graph: GraphsTuple, episode: int):
+        return (graph.states[episode, :, 3].double().cpu().numpy(),  # (T, 4) body rows
+                self._obstacles_of(graph)[episode, 0, 0].double().cpu().numpy())  # (8,)
+
+    def _header_text(self, host, t: int, costs_t, reward_t):
+        return "", vmas_header_lines(self, host[0][t], host[1], costs_t, t)
+
+
+def _angle_dist(a: float, b: float) -> float:
+    """The reference's angle_dist_np: a - b wrapped into (-pi, pi]."""
+    return float(np.arctan2(np.sin(a - b), np.cos(a - b)))
+
+
+def vmas_header_lines(env: VMASEnv, body_row, record, costs_t, kk: int) -> list:
+    """The right-aligned header lines of one video frame, top to bottom, as the reference formats them
+    (vmas_wheel.py:407-413, vmas_reverse_transport.py:413-422).  body_row: states[3] (4,), record: the env record (8,),
+    costs_t: (n_cost,) max over agents; all read as float64 on the host."""
+    body, rec = np.asarray(body_row, dtype=np.float64), np.asarray(record, dtype=np.float64).reshape(-1)
+    if env.ENGINE == _lib.DGPPO_ENGINE_VMAS_WHEEL:
+        return [f"omega={body[1]:+.3f}", f"kk={kk:04}", f"dist_obs={_angle_dist(body[0], rec[1]):.3f}",
+                f"dist_goal={_angle_dist(body[0], rec[0]):.3f}"]
+    cost = ", ".join(f"{c:+.3f}" for c in np.asarray(costs_t, dtype=np.float64).reshape(-1))
+    d_obs = np.linalg.norm(body[None, :2] - rec[2:8].reshape(3, 2), axis=-1) - 0.15  # obs_radius
+    return [f"cost={cost}", f"kk={kk:04}", "dist_obs=[" + ", ".join(f"{d:+.3f}" for d in d_obs) + "]",
+            f"dist_goal={np.linalg.norm(body[:2] - rec[0:2]):.3f}"]
+
 
 class VMASWheel(VMASEnv):
     """vmas_wheel.py:35-307."""
@@ -199,4 +257,5 @@ class VMASReverseTransport(VMASEnv):
                                          rec[..., 0, 2:].unflatten(-1, (3, 2)) if rec is not None else None, rec)
 
 
-__all__ = ["VMASEnv", "VMASWheel", "VMASReverseTransport", "VMASWheelState", "VMASReverseTransportState"]
+__all__ = ["VMASEnv", "VMASWheel", "VMASReverseTransport", "VMASWheelState", "VMASReverseTransportState",
+           "vmas_header_lines"]

@@ -22,6 +22,7 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::lidar_observe_fov dgppo_lidar_observe_fov  lidar_observe_los with the senders outside the receiver's cone masked too
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
+  dgppo::render_frames_vmas  dgppo_render_frames_vmas  the drawings of vmas_wheel.py / vmas_reverse_transport.py render_video
   dgppo::gnn_attn_fwd   dgppo_gnn_attn_fwd   GraphTransformer attention core, gnn.py:83-117
   dgppo::gnn_attn_bwd   dgppo_gnn_attn_bwd   its gradient (the jax.grad of update_Vl / update_policy)
   dgppo::gae            dgppo_gae            compute_dec_ocp_gae, algo/utils.py:11-79
@@ -528,6 +529,41 @@ def render_frames_field(cfg: int, states: Tensor, receivers: Tensor, senders: Te
 
 
 render_frames_field.register_fake(_returns_none)
+
+
+@torch.library.custom_op("dgppo::render_frames_vmas", mutates_args=("out",))
+def render_frames_vmas(cfg: int, states: Tensor, record: Tensor, out: Tensor) -> None:
+    """Rasterise the frames of a VMASWheel / VMASReverseTransport graph batch: states (B, 4, 4) or (B, T, 4, 4)
+    float32 (agents 0..2, then the body row) and the env record (B, 1, 8), one per episode -> out, a contiguous uint8
+    (B[, T], S, S, 4) RGBA image stack.  The states' batch strides are free (the (B, T) view of a time-major rollout
+    buffer passes without a copy); the trailing dims must be contiguous.  No edges are drawn, so none are passed."""
+    _lib.require_gpu(states.device, "dgppo::render_frames_vmas")
+    _lib.require_gpu(out.device, "dgppo::render_frames_vmas")
+    nb = states.dim() - 2
+    if nb not in (1, 2) or tuple(states.shape[-2:]) != (4, 4) or states.dtype != torch.float32:
+        raise ValueError("render_frames_vmas: float32 states (B[, T], 4, 4)")
+    if record.dim() != 3 or tuple(record.shape) != (states.shape[0], 1, _lib.DGPPO_VMAS_FIELDS) or \
+            record.dtype != torch.float32 or record.device != states.device:
+        raise ValueError("render_frames_vmas: record must be float32 (B, 1, 8) on the states' device, one per episode")
+    frames = int(states.shape[0]) * (int(states.shape[1]) if nb == 2 else 1)
+    if out.dtype != torch.uint8 or out.dim() < 3 or not out.is_contiguous() or out.shape[-1] != 4 or \
+            out.shape[-2] != out.shape[-3] or out.numel() != frames * 4 * int(out.shape[-2]) ** 2:
+        raise ValueError("render_frames_vmas: out must be a contiguous uint8 (frames, S, S, 4) tensor")
+    _stride(states, 2)  # raises unless the trailing dims are contiguous
+    _stride(record, 2)
+    a = _lib.RenderArgs()
+    a.states, a.states_estride, a.states_tstride = _p(states), states.stride(0), (states.stride(1) if nb == 2 else 0)
+    a.obstacles, a.obstacles_estride = _p(record), record.stride(0)
+    a.out = _p(out)
+    a.n_frames, a.frames_per_episode = frames, (int(states.shape[1]) if nb == 2 else 1)
+    a.size, a.flags = int(out.shape[-2]), 0
+    if a.n_frames == 0:
+        return
+    _lib.check(_lib.load().dgppo_render_frames_vmas(ctypes.byref(env_cfg(cfg)), ctypes.byref(a), _stream(states)),
+               "dgppo_render_frames_vmas")
+
+
+render_frames_vmas.register_fake(_returns_none)
 
 
 # ---- GraphTransformer attention core -------------------------------------------------------------------

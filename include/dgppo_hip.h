@@ -381,7 +381,7 @@ int dgppo_make_rectangles(int64_t count, const float* center, const float* width
  * The pixel rule, the shapes' signed distances and the layer order are DESIGN.md's "Rendering" section.  Edge indices
  * outside [0, N) and primitives with a non-finite coordinate are skipped, so caller-made graphs cannot cause an
  * out-of-bounds read.  One launch on `stream`, no atomics: the same inputs give the same bytes.
- * DGPPO_EINVAL: the VMAS engines, size < 1 (or > 32768), n_frames < 0, frames_per_episode < 1, a NULL required
+ * DGPPO_EINVAL: the VMAS engines (theirs is dgppo_render_frames_vmas, below), size < 1 (or > 32768), n_frames < 0, frames_per_episode < 1, a NULL required
  * pointer, a negative stride, or `out` overlapping the bytes an input spans. */
 #define DGPPO_RENDER_FOV 1 /* flags bit 0: draw the FoV wedges (Omni engine) */
 typedef struct dgppo_render_args {
@@ -418,6 +418,19 @@ typedef struct dgppo_render_field {
 
 int dgppo_render_frames_field(const dgppo_env_cfg* cfg, const dgppo_render_args* a, const dgppo_render_field* field,
                               void* stream);
+
+/* The frames of the two VMAS engines (the reference's vmas_wheel.py:317-422 / vmas_reverse_transport.py:322-431
+ * render_video drawings) by the same pixel rule, kernel layout and dgppo_render_args: `states` are the (4, sd) rows
+ * (agents 0..2, then the body row), `obstacles` the env record (DGPPO_VMAS_FIELDS floats per episode, reached through
+ * obstacles_estride); receivers / senders are not read and may be NULL (no edges are drawn); flags must be 0.  The view
+ * is the square of side V = m * area_size about the origin, m = 1.02 (Wheel) / 1.01 (Transport), h = V / size, pixel
+ * (row, col) samples (-V/2 + (col + 0.5) h, V/2 - (row + 0.5) h).  Wheel, bottom to top: avoid sector, the line's two
+ * halves, goal ray, agents 0..2; Transport: arena outline, goal, obstacles, box outline, agents 0..2, box centre
+ * (DESIGN.md "Rendering" has the tables).  A primitive with a non-finite input is skipped.  One launch, no atomics.
+ * DGPPO_EINVAL without a launch: any other engine, flags != 0, and what dgppo_render_frames rejects (sizes, a NULL
+ * states / out / record, a negative stride, the grid limit, `out` overlapping the states or the records);
+ * n_frames == 0 returns 0.  No ABI number change (a new symbol only). */
+int dgppo_render_frames_vmas(const dgppo_env_cfg* cfg, const dgppo_render_args* a, void* stream);
 
 /* T env steps with given actions in one call: replaces the env half of the reference's rollout scan
  * `lax.scan(body, ...)` over env.step (dgppo/trainer/utils.py:45-55) for a fixed action sequence.

@@ -19,7 +19,9 @@ over --video).  The metric lines are the same with and without --video.
 `--cbf AGENT` (with --video) draws the learned safety value under each rendered episode: h = -max over the cost
 components of Vh, had agent AGENT stood at each node of a `--cbf-grid` G x G grid (default 32) with everything else
 and the carry fixed (utils/field.py value_field).  Red is predicted unsafe, blue safe, the black line the boundary of
-the learned safe set.  It needs an algorithm with get_Vh (dgppo, hcbfcrpo).
+the learned safe set.  It needs an algorithm with get_Vh (dgppo, hcbfcrpo).  The VMAS envs render through the same
+--video path (their own pictures: env/vmas render_frames); --cbf is refused for them, since they have no get_graph of
+given states to sweep.
 
 Beyond the reference: `--scene PATH` evaluates on the initial states stored in a scene file
 (dgppo_fov_amd/utils/scene.py) instead of seeds -- episodes are rows [offset:epi] of the file, all of its rows when
@@ -60,9 +62,14 @@ def test(args):
 
     np.random.seed(args.seed)
     cfg = _config(args.path)
+    env_id = cfg["env"] if args.env is None else args.env
+    if args.cbf is not None and args.video and not args.no_video and str(env_id).startswith("VMAS"):
+        # refused before anything is loaded or run
+        raise SystemExit(f"--cbf is not built for {env_id}: the VMAS envs have no get_graph of given states, so the "
+                         "value sweep that draws the field cannot be run")
     dev = torch.device("cuda", 0)
     num_agents = cfg["num_agents"] if args.num_agents is None else args.num_agents
-    env = make_env(env_id=cfg["env"] if args.env is None else args.env, num_agents=num_agents,
+    env = make_env(env_id=env_id, num_agents=num_agents,
                    num_obs=cfg["obs"] if args.obs is None else args.obs, n_rays=cfg.get("n_rays", 32),
                    max_step=args.max_step, full_observation=args.full_observation, device=dev)
     algo = make_algo(cfg["algo"], env=env, node_dim=env.node_dim, edge_dim=env.edge_dim, state_dim=env.state_dim,
