@@ -22,7 +22,9 @@
 // the same wave, so the gate math is register local.
 //
 // Same math as the unfused path (nn/layers.py, algo/module/nets.py); summation orders differ, so
-// results agree to fp32 rounding (tests/test_rollout_gpu.py checks both against float64).
+// results agree to fp32 rounding (tests/test_rollout_gpu.py checks both against float64 on env graphs;
+// tests/test_policy_direct_gpu.py holds this kernel alone to the float64 reference of tests/policy_ref.py across
+// what dgppo_policy_step_supported accepts, and tests/test_policy_ref_cpu.py checks the host-side contract).
 #include <hip/hip_runtime.h>
 
 #include "lds_attr.h"
@@ -724,7 +726,7 @@ extern "C" int dgppo_policy_step_supported(const dgppo_policy_step_args* p) {
   if (!p) return 0;
   if (p->n_agents < 1 || p->n_agents > dgppo::kRows || p->C < 1 || p->C > dgppo::kCP || p->D0 < 1 ||
       p->D0 > dgppo::kMaxD0 || p->A < 1 || p->A > 4 || p->H != dgppo::kH || p->ED < 4 ||
-      p->ED > 4 + dgppo::kMaxEX)
+      p->ED > 4 + dgppo::kMaxEX || p->N < p->n_agents)
     return 0;
   for (int l = 0; l < p->n_layers && l < 2; ++l)
     if (p->ED > 4 && !p->layer[l].Wex) return 0;
@@ -753,7 +755,9 @@ extern "C" int dgppo_policy_step(const dgppo_policy_step_args* p, void* stream) 
   if (ngroups > INT32_MAX) return DGPPO_EINVAL;
   const int64_t grid = ngroups;
   const bool wide = p->D0 > dgppo::kNarrowD0 || p->ED > 4;
-  const bool np = !wide && p->n_layers == 2 && (int64_t)gpg * (p->N - p->n_agents) <= dgppo::kPreMax;
+  // the node table needs at least one never-receiving node per graph: its staging loop divides by N - n_agents
+  const bool np = !wide && p->n_layers == 2 && p->N > p->n_agents &&
+                  (int64_t)gpg * (p->N - p->n_agents) <= dgppo::kPreMax;
   const void* fn = wide ? (const void*)dgppo::policy_step_kernel<dgppo::kMaxD0, dgppo::kMaxEX>
                         : (np ? (const void*)dgppo::policy_step_kernel<dgppo::kNarrowD0, 0, true>
                               : (const void*)dgppo::policy_step_kernel<dgppo::kNarrowD0, 0>);

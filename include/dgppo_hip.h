@@ -818,7 +818,12 @@ int dgppo_gru_set_form(int32_t regb);
  * Parameter pointers are the layouts of dgppo_fov_amd/nn/layers.py (GraphTransformer: Wq (D, H F),
  * bq, Wkt (H, F, D), bk, Wcat (H (D+5), F) = [Wv; We; bv], Wu (D, F), bu; GRU Wi (64, 192) [r|z|n],
  * bi, Wh (64, 192), bhn).  dgppo_policy_step_supported() tells whether a configuration fits the
- * fused kernel (n <= 32, C <= 32, D0 <= 8, H = 3, actor GNN D0->32->64 or D0->64, A in {1, 2, 4}).
+ * fused kernel (1 <= n <= 16, N >= n, 1 <= C <= 32, 1 <= D0 <= 12, H = 3, 4 <= ED <= 10 with Wex on every layer
+ * in use when ED > 4, actor GNN D0->32->64 or D0->64, A in 1..4); dgppo_policy_prepare / dgppo_policy_step return
+ * DGPPO_EINVAL for anything else.  N >= n_agents is required: nodes 0..n-1 are the agents (N == n: an all-agent
+ * graph).  For ED == 4 the kernel loads edge rows as 16-byte vectors: `edges` and edges_gstride * 4 bytes must be
+ * 16-byte aligned (edges_gstride a multiple of 4 floats); wider edge rows carry no alignment requirement.  The graph
+ * strides may exceed the rows they hold; the pad is never read.
  * `work` (dgppo_policy_work_floats() floats) holds the per-layer query-key products
  * [Wq_h Wkt_h | Wq_h bk_h] and their biases; dgppo_policy_prepare() fills it from the current weights
  * and must run after every weight change (the rollouts call it once per rollout, inside the graph). */
