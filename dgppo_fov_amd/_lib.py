@@ -174,7 +174,8 @@ class EnvGraphHitsIO(ctypes.Structure):  # dgppo_env_graph_hits_io
 
 OBSERVE_NOISE, OBSERVE_DROPOUT = 1, 2  # include/dgppo_hip.h DGPPO_OBSERVE_*
 OBSERVE_SIGHT = 4  # dgppo_lidar_observe_los and dgppo_lidar_observe_fov
-OBSERVE_FOV = 8  # dgppo_lidar_observe_fov only
+OBSERVE_FOV = 8  # dgppo_lidar_observe_fov and dgppo_lidar_observe_bodies
+OBSERVE_BODIES = 16  # dgppo_lidar_observe_bodies only
 
 
 class LidarObserveIO(ctypes.Structure):  # dgppo_lidar_observe_io
@@ -454,6 +455,9 @@ SIGNATURES = {
     "dgppo_agent_fov": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(AgentFovIO), ctypes.c_void_p]),
     "dgppo_lidar_observe_fov": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO),
                                                ctypes.c_float, ctypes.c_void_p]),
+    "dgppo_lidar_scan_bodies": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarScanIO), ctypes.c_void_p]),
+    "dgppo_lidar_observe_bodies": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(LidarObserveIO),
+                                                  ctypes.c_float, ctypes.c_void_p]),
     "dgppo_make_rectangles": (ctypes.c_int, [_I64, _V, _V, _V, _V, _V]),
     "dgppo_render_frames": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs), ctypes.c_void_p]),
     "dgppo_render_frames_field": (ctypes.c_int, [ctypes.POINTER(EnvCfg), ctypes.POINTER(RenderArgs),

@@ -29,7 +29,7 @@ from ..nn import kernels as K
 from ..nn.layers import GraphBatch
 from ..trainer.data import Rollout
 from ..trainer.rollout import NoisyLidarRolloutEngine, RolloutEngine
-from ..utils.sensor import Sensing
+from ..utils.sensor import Sensing, bodies_option
 from .module.nets import ActorNet, VhNet, VlNet
 
 
@@ -140,7 +140,7 @@ class DGPPO:
                  cbf_eps: float = 1e-2, cbf_weight: float = 1.0, train_steps: int = int(1e5),
                  cbf_schedule: bool = True, device=None, lidar_noise: Optional[float] = None,
                  lidar_dropout: Optional[float] = None, lidar_occlusion: bool = False,
-                 lidar_fov: Optional[float] = None, **kwargs):
+                 lidar_fov: Optional[float] = None, lidar_bodies: bool = False, **kwargs):
         if rnn_layers < 1:
             raise ValueError(f"rnn_layers {rnn_layers} < 1")
         self._env = env
@@ -153,6 +153,10 @@ class DGPPO:
         # ValueError for an algorithm or env that cannot train under them and for values outside their domains
         self.sensing = Sensing.of(env, "lidar_fov", lidar_noise, lidar_dropout, lidar_occlusion, lidar_fov,
                                   algo_cls=type(self))
+        # lidar_bodies: the observed graphs' beams also return off the other agents' bodies (env.observe(bodies=True)), so
+        # a neighbour whose edge is hidden still shows up as a hit row; on its own it selects the same engine.  It
+        # travels beside the record
+        self.bodies = bodies_option(env, "lidar_bodies", lidar_bodies, algo_cls=type(self))
         self.device = torch.device(device) if device is not None else env.device
         self._node_dim, self._edge_dim, self._action_dim, self._n_agents = node_dim, edge_dim, action_dim, n_agents
         self.actor_gnn_layers, self.Vl_gnn_layers, self.Vh_gnn_layers = actor_gnn_layers, Vl_gnn_layers, Vh_gnn_layers
@@ -315,9 +319,9 @@ class DGPPO:
 
     @property
     def sensed(self) -> bool:
-        """Whether collect and det_rollout return observed graphs (a sensor model, occlusion, a field of view, or any
-        of them together)."""
-        return self.sensing is not None
+        """Whether collect and det_rollout return observed graphs (a sensor model, occlusion, a field of view, body
+        returns, or any of them together)."""
+        return self.sensing is not None or self.bodies
 
     def _rollout_lanes(self, n_env: int) -> int:
         """Env slices on separate streams (RolloutEngine lanes): DGPPO_ROLLOUT_LANES when the slices are
@@ -331,7 +335,7 @@ class DGPPO:
             if self.sensed:
                 eng = NoisyLidarRolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                               env_offset=self.rank * n_env, actor=self.actor, mode=mode,
-                                              sensing=self.sensing)
+                                              sensing=self.sensing, bodies=self.bodies)
             else:
                 eng = RolloutEngine(self._env, n_env, self._env.max_episode_steps, self.device,
                                     env_offset=self.rank * n_env, actor=self.actor, mode=mode,

@@ -538,6 +538,39 @@ __device__ __forceinline__ float beam_alpha(const float* obst, const float* evec
   return a * (1.0f - *is_in);
 }
 
+// The same beam against the other agents' bodies, discs of radius rho around columns 0, 1 of `rows` (pitch
+// row_stride): the smallest alpha at which it enters one, 0 when the start is inside or on one, 1e6 when none is met
+// (include/dgppo_hip.h has the expressions).  Every comparison fails on NaN, so a NaN or infinite row returns nothing.
+__device__ __forceinline__ float body_alpha(const float* rows, int row_stride, int n, int i, float sx, float sy,
+                                            float dx, float dy, float rho) {
+  const float rr = rho * rho;
+  const float aa = dx * dx + dy * dy;
+  float best = 1e6f;
+#pragma unroll 1
+  for (int j = 0; j < n; ++j) {
+    if (j == i) continue;
+    const float mx = rows[j * row_stride + 0] - sx;
+    const float my = rows[j * row_stride + 1] - sy;
+    const float cc = (mx * mx + my * my) - rr;
+    const float bb = dx * mx + dy * my;
+    const float disc = bb * bb - aa * cc;
+    float tj = 1e6f;
+    if (cc <= 0.0f) {
+      tj = 0.0f;
+    } else if (bb > 0.0f && disc >= 0.0f) {
+      const float t = (bb - sqrtf(disc)) / aa;
+      if (t >= 0.0f && t <= 1.0f) tj = t;
+    }
+    best = tj < best ? tj : best;
+  }
+  return best;
+}
+
+// What the scan ranks once the bodies return too: the obstacle alpha's NaN propagates, else the nearer of the two.
+__device__ __forceinline__ float nearer_alpha(float a_obs, float a_body) {
+  return a_obs != a_obs ? a_obs : (a_body < a_obs ? a_body : a_obs);
+}
+
 // The hit point of that beam at alpha a: start + (end - start) * a with the end formed first, as the reference
 // does (sx + dx * a differs in fp32).
 __device__ __forceinline__ float2 beam_point(float sx, float sy, float dx, float dy, float a) {
@@ -3054,8 +3087,12 @@ __device__ __forceinline__ Carve scan_carve() {
 constexpr int kScanLds = kMaxObs * DGPPO_OBST_FIELDS + kMaxObs * 8 + 4;
 
 // dgppo_lidar_scan: one wave per (env, agent), lanes over rays.  alpha[r] = beam_alpha, ray by ray.
+// BODIES (dgppo_lidar_scan_bodies): the env's n agent positions staged behind the obstacle records, as
+// lidar_sight_kernel does, and alpha[r] = nearer_alpha(beam_alpha, body_alpha).
+constexpr int kSightLds = kScanLds + 2 * kMaxAgents;
+template <bool BODIES = false>
 __global__ __launch_bounds__(64) void lidar_alpha_kernel(dgppo_env_cfg cfg, dgppo_lidar_scan_io io) {
-  __shared__ __attribute__((aligned(16))) float lds[kScanLds];
+  __shared__ __attribute__((aligned(16))) float lds[BODIES ? kSightLds : kScanLds];
   const int n = cfg.n_agents, O = cfg.n_obs, R = cfg.n_rays, sd = cfg.state_dim;
   const int lane = threadIdx.x;
   const int64_t env = blockIdx.x / n;
@@ -3068,6 +3105,10 @@ __global__ __launch_bounds__(64) void lidar_alpha_kernel(dgppo_env_cfg cfg, dgpp
   const float* ob = io.obstacles + env * io.obstacles_stride;
   for (int idx = lane; idx < O * DGPPO_OBST_FIELDS; idx += 64) obst[idx] = ob[idx];
   if (lane < 2) xy[lane] = io.agent[env * io.agent_stride + i * sd + lane];
+  if constexpr (BODIES) {
+    const float* ag = io.agent + env * io.agent_stride;
+    for (int idx = lane; idx < 2 * n; idx += 64) lds[kScanLds + idx] = ag[(idx >> 1) * sd + (idx & 1)];
+  }
   __syncthreads();
   stage_edge_vectors(O, lds, cv, lane, 64);
   if (lane == 0) agent_is_inside(O, lds, cv, 2, 0);
@@ -3075,8 +3116,12 @@ __global__ __launch_bounds__(64) void lidar_alpha_kernel(dgppo_env_cfg cfg, dgpp
   const float sx = xy[0], sy = xy[1];
   float* out = io.alpha + env * io.alpha_stride + (int64_t)i * R;
 #pragma unroll 1
-  for (int r = lane; r < R; r += 64)
-    out[r] = beam_alpha(obst, evec, O, sx, sy, io.ray_dirs[2 * r + 0], io.ray_dirs[2 * r + 1], isin);
+  for (int r = lane; r < R; r += 64) {
+    const float dx = io.ray_dirs[2 * r + 0], dy = io.ray_dirs[2 * r + 1];
+    float a = beam_alpha(obst, evec, O, sx, sy, dx, dy, isin);
+    if constexpr (BODIES) a = nearer_alpha(a, body_alpha(lds + kScanLds, 2, n, i, sx, sy, dx, dy, cfg.car_radius));
+    out[r] = a;
+  }
 }
 
 // dgppo_lidar_hits: one wave per (env, agent): rank_below over the sort_keys of the caller's alphas, beam_point for
@@ -3218,7 +3263,6 @@ __device__ __forceinline__ void mark_pairs(uint8_t* out, uint8_t hidden, int n, 
 
 // dgppo_lidar_sight: one wave per env.  Obstacle records and edge vectors staged as in lidar_alpha_kernel, the
 // agents' positions behind them.  visible = mark_pairs<SIGHT> with hidden = 0.
-constexpr int kSightLds = kScanLds + 2 * kMaxAgents;
 __global__ __launch_bounds__(64) void lidar_sight_kernel(dgppo_env_cfg cfg, dgppo_lidar_sight_io io) {
   __shared__ __attribute__((aligned(16))) float lds[kSightLds];
   const int n = cfg.n_agents, O = cfg.n_obs, sd = cfg.state_dim;
@@ -3263,7 +3307,9 @@ __global__ __launch_bounds__(64) void agent_fov_kernel(dgppo_env_cfg cfg, dgppo_
 // are untouched.  The cone's cosine arrives as cfg.c_cos_fov: the entry launches with a copy of the cfg that holds the
 // sensed cone there (this kernel evaluates no cost, so nothing else reads the field), which leaves the kernel's
 // arguments as they were.
-template <int ENGINE, int GOAL, int SD, int BLOCK, bool SIGHT = false, bool FOV = false>
+// BODIES (dgppo_lidar_observe_bodies with DGPPO_OBSERVE_BODIES): each alpha becomes nearer_alpha(beam_alpha, body_alpha
+// over the agent rows in nxt) in registers, before the sensor model; no LDS beyond the carve.
+template <int ENGINE, int GOAL, int SD, int BLOCK, bool SIGHT = false, bool FOV = false, bool BODIES = false>
 __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg, dgppo_lidar_observe_io io) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Dims<0, -1, 0, 0> d(cfg);
@@ -3300,8 +3346,11 @@ __global__ __launch_bounds__(BLOCK) void lidar_observe_kernel(dgppo_env_cfg cfg,
 #pragma unroll 1
   for (int q = tid; q < n * R; q += BLOCK) {
     const int i = q / R, r = q - i * R;
-    const float a = beam_alpha(obst, evec, O, nxt[i * SD + 0], nxt[i * SD + 1], io.ray_dirs[2 * r + 0],
-                               io.ray_dirs[2 * r + 1], lds + cv.isin + i);
+    float a = beam_alpha(obst, evec, O, nxt[i * SD + 0], nxt[i * SD + 1], io.ray_dirs[2 * r + 0],
+                         io.ray_dirs[2 * r + 1], lds + cv.isin + i);
+    if constexpr (BODIES)
+      a = nearer_alpha(a, body_alpha(nxt, SD, n, i, nxt[i * SD + 0], nxt[i * SD + 1], io.ray_dirs[2 * r + 0],
+                                     io.ray_dirs[2 * r + 1], cfg.car_radius));
     float seen = a;
     if (io.flags & DGPPO_OBSERVE_NOISE) {
       const float x = a + noise::normal_at(e0 + q, seed, stream) * io.noise_scale;
@@ -4576,14 +4625,24 @@ static int validate_sensor(const dgppo_env_cfg* cfg) {
   return 0;
 }
 
-extern "C" int dgppo_lidar_scan(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream) {
+// dgppo_lidar_scan and dgppo_lidar_scan_bodies: the same checks, one wave per (env, agent)
+template <bool BODIES>
+static int lidar_scan_launch(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream) {
   if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
   if (io->n_env == 0) return 0;
   if (!io->agent || !io->obstacles || !io->ray_dirs || !io->alpha) return DGPPO_EINVAL;
   const int64_t waves = (int64_t)io->n_env * cfg->n_agents;  // one per (env, agent)
   if (waves > INT32_MAX) return DGPPO_EINVAL;
-  hipLaunchKernelGGL(lidar_alpha_kernel, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, *cfg, *io);
+  hipLaunchKernelGGL(lidar_alpha_kernel<BODIES>, dim3((unsigned)waves), dim3(64), 0, (hipStream_t)stream, *cfg, *io);
   return (int)hipGetLastError();
+}
+
+extern "C" int dgppo_lidar_scan(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream) {
+  return lidar_scan_launch<false>(cfg, io, stream);
+}
+
+extern "C" int dgppo_lidar_scan_bodies(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream) {
+  return lidar_scan_launch<true>(cfg, io, stream);
 }
 
 extern "C" int dgppo_lidar_hits(const dgppo_env_cfg* cfg, const dgppo_lidar_hits_io* io, void* stream) {
@@ -4647,8 +4706,18 @@ extern "C" int dgppo_agent_fov(const dgppo_env_cfg* cfg, const dgppo_agent_fov_i
   return (int)hipGetLastError();
 }
 
-// dgppo_lidar_observe, dgppo_lidar_observe_los and dgppo_lidar_observe_fov: the same checks and launch, `allowed` the
-// entry's flag bits, `deg` the cone's half angle (read with DGPPO_OBSERVE_FOV only)
+// dgppo_lidar_observe, dgppo_lidar_observe_los, dgppo_lidar_observe_fov and dgppo_lidar_observe_bodies: the same checks
+// and launch, `allowed` the entry's flag bits, `deg` the cone's half angle (read with DGPPO_OBSERVE_FOV only)
+template <int ENGINE, int GOAL, int SD, bool SIGHT, bool FOV>
+static void lidar_observe_launch(const dgppo_env_cfg& cfg, const dgppo_lidar_observe_io& io, size_t shmem, hipStream_t s) {
+  if (io.flags & DGPPO_OBSERVE_BODIES)
+    hipLaunchKernelGGL((lidar_observe_kernel<ENGINE, GOAL, SD, 128, SIGHT, FOV, true>), dim3((unsigned)io.n_env),
+                       dim3(128), shmem, s, cfg, io);
+  else
+    hipLaunchKernelGGL((lidar_observe_kernel<ENGINE, GOAL, SD, 128, SIGHT, FOV>), dim3((unsigned)io.n_env), dim3(128),
+                       shmem, s, cfg, io);
+}
+
 static int lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, void* stream, int allowed,
                          float deg = 180.0f) {
   if (validate_sensor(cfg) || !io || io->n_env < 0) return DGPPO_EINVAL;
@@ -4669,27 +4738,24 @@ static int lidar_observe(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io*
   const Carve cv(cfg->n_agents, cfg->state_dim, cfg->n_obs, cfg->n_rays, cfg->top_k, true);
   const size_t shmem = (size_t)cv.total * sizeof(float);
   if (shmem > 64 * 1024) return DGPPO_EINVAL;
+  const hipStream_t s = (hipStream_t)stream;
   visit_engine_goal(*cfg, [&](auto e) {
     using E = decltype(e);
     if constexpr ((E::ENGINE == DGPPO_ENGINE_BICYCLE || E::ENGINE == DGPPO_ENGINE_OMNI) &&
-                  E::GOAL == DGPPO_GOAL_TARGET) {  // LidarBicycleTarget, LidarOmniTarget: four kernels
+                  E::GOAL == DGPPO_GOAL_TARGET) {  // LidarBicycleTarget, LidarOmniTarget: four kernels more, twice
       if (fov) {
         if (io->flags & DGPPO_OBSERVE_SIGHT)
-          hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, true, true>),
-                             dim3((unsigned)io->n_env), dim3(128), shmem, (hipStream_t)stream, seen, *io);
+          lidar_observe_launch<E::ENGINE, E::GOAL, E::SD, true, true>(seen, *io, shmem, s);
         else
-          hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, false, true>),
-                             dim3((unsigned)io->n_env), dim3(128), shmem, (hipStream_t)stream, seen, *io);
+          lidar_observe_launch<E::ENGINE, E::GOAL, E::SD, false, true>(seen, *io, shmem, s);
         return;
       }
     }
     if constexpr (E::ENGINE != DGPPO_ENGINE_MPE) {
       if (io->flags & DGPPO_OBSERVE_SIGHT)
-        hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128, true>), dim3((unsigned)io->n_env),
-                           dim3(128), shmem, (hipStream_t)stream, *cfg, *io);
+        lidar_observe_launch<E::ENGINE, E::GOAL, E::SD, true, false>(*cfg, *io, shmem, s);
       else
-        hipLaunchKernelGGL((lidar_observe_kernel<E::ENGINE, E::GOAL, E::SD, 128>), dim3((unsigned)io->n_env), dim3(128),
-                           shmem, (hipStream_t)stream, *cfg, *io);
+        lidar_observe_launch<E::ENGINE, E::GOAL, E::SD, false, false>(*cfg, *io, shmem, s);
     }
   });
   return (int)hipGetLastError();
@@ -4707,6 +4773,14 @@ extern "C" int dgppo_lidar_observe_fov(const dgppo_env_cfg* cfg, const dgppo_lid
                                        float half_angle_deg, void* stream) {
   return lidar_observe(cfg, io, stream,
                        DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT | DGPPO_OBSERVE_SIGHT | DGPPO_OBSERVE_FOV,
+                       half_angle_deg);
+}
+
+extern "C" int dgppo_lidar_observe_bodies(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io,
+                                          float half_angle_deg, void* stream) {
+  return lidar_observe(cfg, io, stream,
+                       DGPPO_OBSERVE_NOISE | DGPPO_OBSERVE_DROPOUT | DGPPO_OBSERVE_SIGHT | DGPPO_OBSERVE_FOV |
+                           DGPPO_OBSERVE_BODIES,
                        half_angle_deg);
 }
 

@@ -478,14 +478,22 @@ class MultiAgentEnv(ABC):
         B = int(agent_states.shape[0])
         return self._sensor_arg(what, "agent_states", agent_states, (B, self._num_agents, self.state_dim))
 
-    def lidar_scan(self, agent_states: torch.Tensor, obstacles) -> torch.Tensor:
+    def lidar_scan(self, agent_states: torch.Tensor, obstacles, bodies: bool = False) -> torch.Tensor:
         """The raw scan (torch.ops.dgppo.lidar_scan): alpha (B, n, R) of the agents at `agent_states` (B, n, sd)
         among `obstacles` (a Rectangle or its packed (B, O, 16) tensor): per beam the fraction of the sensing range
         to the nearest obstacle edge, 1e6 where nothing is hit, 0 for an agent inside an obstacle -- the values
         get_lidar_data ranks (env/utils.py:115-130).  `lidar_hits(agent_states, alpha)` turns them (or an edited
-        copy: utils/sensor.py) into hit points."""
+        copy: utils/sensor.py) into hit points.
+
+        bodies: the beams also return off the other agents' bodies, discs of radius car_radius
+        (torch.ops.dgppo.lidar_scan_bodies): per beam the nearer of the obstacle and the body return, 0 where the
+        discs overlap; a NaN or infinite row returns nothing, an obstacle NaN propagates.  False takes exactly the
+        path without it.  The env's own step, reward and cost never see bodies."""
+        from ..utils.sensor import bodies_option
+
         what = "lidar_scan"
         self._require_lidar(what)
+        op = torch.ops.dgppo.lidar_scan_bodies if bodies_option(self, what, bodies) else torch.ops.dgppo.lidar_scan
         agent = self._sensor_agents(what, agent_states)
         B = int(agent.shape[0])
         ob = self._sensor_arg(what, "obstacles", getattr(obstacles, "packed", obstacles),
@@ -493,7 +501,7 @@ class MultiAgentEnv(ABC):
         _lib.require_gpu(agent.device, "env.lidar_scan")
         alpha = torch.empty((B, self._num_agents, int(self._params["n_rays"])), dtype=torch.float32,
                             device=agent.device)
-        torch.ops.dgppo.lidar_scan(self._cfg_handle, agent, ob, self._ray_table(agent.device), alpha)
+        op(self._cfg_handle, agent, ob, self._ray_table(agent.device), alpha)
         return alpha
 
     def lidar_hits(self, agent_states: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:
@@ -567,7 +575,8 @@ class MultiAgentEnv(ABC):
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
     def observe(self, state, t: int, *, sigma: float, dropout: float, seed, env_offset: int = 0,
-                out: Optional[GraphsTuple] = None, occlusion: bool = False, fov=None) -> GraphsTuple:
+                out: Optional[GraphsTuple] = None, occlusion: bool = False, fov=None,
+                bodies: bool = False) -> GraphsTuple:
         """The OBSERVED graph of the true `state` (get_graph's tuple, obstacles required) at step `t` under the
         range-noise / beam-dropout sensor model of utils/sensor.py, in one HIP launch (torch.ops.dgppo.lidar_observe):
         bit for bit `get_graph(state, lidar_data=lidar_hits(agent, LidarNoise(sigma, dropout, seed,
@@ -585,11 +594,16 @@ class MultiAgentEnv(ABC):
         is outside the receiver's forward cone goes to the pad node as well, `mask_unseen(observe(...),
         field_of_view(agent, fov) [& line_of_sight(agent, obstacle)])` bit for bit, in the same launch
         (torch.ops.dgppo.lidar_observe_fov).  The beams stay omnidirectional.  None and 180 take exactly the paths
-        without it."""
-        from ..utils.sensor import Sensing, drop_below
+        without it.
+
+        bodies: the beams also return off the other agents' bodies -- `lidar_scan(agent, obstacle, bodies=True)` in
+        place of the scan above, in the same launch (torch.ops.dgppo.lidar_observe_bodies): a neighbour whose edge is
+        hidden or out of range still shows up as an anonymous hit row.  False takes exactly the paths without it."""
+        from ..utils.sensor import Sensing, bodies_option, drop_below
 
         what = "observe"
         sensing = Sensing.of(self, what, sigma, dropout, occlusion, fov)  # checks the env and all four options
+        bodies = bodies_option(self, what, bodies)
         sigma, dropout, fov = sensing.sigma, sensing.dropout, sensing.fov
         sense_range = float(self._params["comm_radius"])
         t, env_offset = int(t), int(env_offset)
@@ -611,11 +625,11 @@ class MultiAgentEnv(ABC):
         if self.cfg.variant != _lib.DGPPO_VARIANT_NONE:
             model = sensing.model(sense_range)
             if not occlusion:
-                return self._observe_chained(model, agent, goal, third, t, seed, env_offset, g)
+                return self._observe_chained(model, agent, goal, third, t, seed, env_offset, g, bodies)
             from ..utils.sensor import mask_unseen
 
             visible = self.line_of_sight(agent, third)  # before the graph is written: `out` may alias the state
-            return mask_unseen(self._observe_chained(model, agent, goal, third, t, seed, env_offset, g), visible)
+            return mask_unseen(self._observe_chained(model, agent, goal, third, t, seed, env_offset, g, bodies), visible)
         iseed = 0 if tkey is not None else int(seed) & 0xFFFFFFFFFFFFFFFF
         flags = (_lib.OBSERVE_NOISE if sigma > 0.0 else 0) | (_lib.OBSERVE_DROPOUT if dropout > 0.0 else 0)
         op = torch.ops.dgppo.lidar_observe
@@ -624,19 +638,23 @@ class MultiAgentEnv(ABC):
         head = (self._cfg_handle, agent, goal, third, self._ray_table(dev), tkey,
                 iseed if iseed < 2 ** 63 else iseed - 2 ** 64, env_offset, t, sigma / sense_range,
                 drop_below(dropout))
-        if fov is not None:  # the heading envs have no variant: always the fused kernel
+        if bodies:
+            flags |= _lib.OBSERVE_BODIES | (_lib.OBSERVE_FOV if fov is not None else 0)
+            torch.ops.dgppo.lidar_observe_bodies(*head, flags, 180.0 if fov is None else fov, g.nodes, g.edges, g.states,
+                                                 g.receivers, g.senders)
+        elif fov is not None:  # the heading envs have no variant: always the fused kernel
             torch.ops.dgppo.lidar_observe_fov(*head, flags | _lib.OBSERVE_FOV, fov, g.nodes, g.edges, g.states,
                                               g.receivers, g.senders)
         else:
             op(*head, flags, g.nodes, g.edges, g.states, g.receivers, g.senders)
         return self._assemble(g.nodes, g.edges, g.states, g.receivers, g.senders, third)
 
-    def _observe_chained(self, model, agent, goal, third, t, seed, env_offset, g) -> GraphsTuple:
+    def _observe_chained(self, model, agent, goal, third, t, seed, env_offset, g, bodies: bool = False) -> GraphsTuple:
         """observe by the three launches with LidarNoise's arithmetic between them (the variant envs)."""
         from ..nn import kernels as K
         from ..utils.sensor import NO_RETURN
 
-        alpha = self.lidar_scan(agent, third)
+        alpha = self.lidar_scan(agent, third, bodies=True) if bodies else self.lidar_scan(agent, third)
         B = alpha.shape[0]
         seen = alpha
         if model.sigma > 0.0 or model.dropout > 0.0:

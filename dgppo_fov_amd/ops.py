@@ -20,6 +20,8 @@ non-CUDA tensor raises NativeLibraryError (`_lib.require_gpu`).
   dgppo::lidar_observe_los dgppo_lidar_observe_los  lidar_observe with the unseen agent-agent edges sent to the pad node
   dgppo::agent_fov      dgppo_agent_fov      which agents lie in each other's forward cone, the FoV cost's arithmetic
   dgppo::lidar_observe_fov dgppo_lidar_observe_fov  lidar_observe_los with the senders outside the receiver's cone masked too
+  dgppo::lidar_scan_bodies dgppo_lidar_scan_bodies  lidar_scan whose beams also return off the other agents' bodies
+  dgppo::lidar_observe_bodies dgppo_lidar_observe_bodies  lidar_observe_fov on lidar_scan_bodies' alphas
   dgppo::render_frames  dgppo_render_frames  the drawing half of env.render_video, env/plot.py render_lidar / render_mpe
   dgppo::render_frames_field  dgppo_render_frames_field  the same under a banded scalar field, plot.py viz_opts["cbf"]
   dgppo::render_frames_vmas  dgppo_render_frames_vmas  the drawings of vmas_wheel.py / vmas_reverse_transport.py render_video
@@ -278,17 +280,36 @@ def lidar_scan(cfg: int, agent: Tensor, obstacles: Tensor, ray_dirs: Tensor, alp
     beam the value get_lidar sorts (1e6 = no return, 0 inside an obstacle, NaN propagates).  Per-env strides are
     free; the trailing dims must be contiguous."""
     _lib.require_gpu(alpha.device, "dgppo::lidar_scan")
+    io = _scan_io(agent, obstacles, ray_dirs, alpha)
+    _lib.check(_lib.load().dgppo_lidar_scan(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(alpha)),
+               "dgppo_lidar_scan")
+
+
+def _scan_io(agent, obstacles, ray_dirs, alpha) -> "_lib.LidarScanIO":
+    """The dgppo_lidar_scan_io of the two scan ops' arguments."""
     io = _lib.LidarScanIO()
     io.agent, io.agent_stride = _p(agent), _stride(agent, 2)
     io.obstacles, io.obstacles_stride = _p(obstacles), _stride(obstacles, 2)
     io.ray_dirs = _p(ray_dirs)
     io.alpha, io.alpha_stride = _p(alpha), _stride(alpha, 2)
     io.n_env = int(agent.shape[0])
-    _lib.check(_lib.load().dgppo_lidar_scan(ctypes.byref(env_cfg(cfg)), ctypes.byref(io), _stream(alpha)),
-               "dgppo_lidar_scan")
+    return io
 
 
 lidar_scan.register_fake(_returns_none)
+
+
+@torch.library.custom_op("dgppo::lidar_scan_bodies", mutates_args=("alpha",))
+def lidar_scan_bodies(cfg: int, agent: Tensor, obstacles: Tensor, ray_dirs: Tensor, alpha: Tensor) -> None:
+    """lidar_scan whose beams also return off the other agents' bodies (discs of radius car_radius around columns 0, 1
+    of the agent rows): per beam the nearer of the obstacle and the body return, an obstacle NaN propagating."""
+    _lib.require_gpu(alpha.device, "dgppo::lidar_scan_bodies")
+    _lib.check(_lib.load().dgppo_lidar_scan_bodies(ctypes.byref(env_cfg(cfg)),
+                                                   ctypes.byref(_scan_io(agent, obstacles, ray_dirs, alpha)),
+                                                   _stream(alpha)), "dgppo_lidar_scan_bodies")
+
+
+lidar_scan_bodies.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::lidar_hits", mutates_args=("hits",))
@@ -423,6 +444,20 @@ def lidar_observe_fov(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, 
 
 
 lidar_observe_fov.register_fake(_returns_none)
+
+
+@torch.library.custom_op("dgppo::lidar_observe_bodies", mutates_args=("nodes", "edges", "states", "receivers", "senders"))
+def lidar_observe_bodies(cfg: int, agent: Tensor, goal: Tensor, obstacles: Tensor, ray_dirs: Tensor,
+                         key: Optional[Tensor], seed: int, env_offset: int, t: int, noise_scale: float, drop_below: float,
+                         flags: int, half_angle_deg: float, nodes: Tensor, edges: Tensor, states: Tensor,
+                         receivers: Tensor, senders: Tensor) -> None:
+    """lidar_observe_fov that also takes OBSERVE_BODIES in `flags`: the beams return off the other agents' bodies too
+    (lidar_scan_bodies' alphas, before the sensor model), in the same launch."""
+    _observe("lidar_observe_bodies", cfg, agent, goal, obstacles, ray_dirs, key, seed, env_offset, t, noise_scale,
+             drop_below, flags, nodes, edges, states, receivers, senders, float(half_angle_deg))
+
+
+lidar_observe_bodies.register_fake(_returns_none)
 
 
 @torch.library.custom_op("dgppo::agent_fov", mutates_args=("in_fov",))

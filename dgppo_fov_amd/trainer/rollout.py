@@ -24,7 +24,7 @@ from ..env.base import MultiAgentEnv
 from ..nn import kernels as K
 from ..nn.layers import GraphBatch
 from ..utils.graph import GraphsTuple
-from ..utils.sensor import Sensing, mask_unseen
+from ..utils.sensor import Sensing, bodies_option, mask_unseen
 from .data import Rollout
 
 
@@ -300,6 +300,10 @@ class _ObservedRolloutEngine(RolloutEngine):
                                   self.obstacles)
 
 
+def _identity_sensor(alpha, t):
+    return alpha
+
+
 class SensorRolloutEngine(_ObservedRolloutEngine):
     """RolloutEngine with a LiDAR sensor model between the world and the policy.
 
@@ -315,28 +319,33 @@ class SensorRolloutEngine(_ObservedRolloutEngine):
     state, and `sensor` may be None (the identity).  fov: a half angle in degrees (the envs with a heading) -- the
     senders outside the receiver's camera cone are hidden too (env.field_of_view, ANDed into the same mask); None and
     180 mean no cone, and `sensor` may be None here as well.  sensing: a utils.sensor.Sensing in place of occlusion and
-    fov, and of `sensor` when that is None (the record's LidarNoise, seed 0).  No hipGraph capture (a sensor is
-    arbitrary Python)."""
+    fov, and of `sensor` when that is None (the record's LidarNoise, seed 0).  bodies: the scan is
+    env.lidar_scan(..., bodies=True), whose beams also return off the other agents' bodies, and `sensor` may be None
+    once more; the true graph's scan stays the obstacle-only one.  No hipGraph capture (a sensor is arbitrary Python)."""
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_DET, sensor=None, init_state=None,
-                 occlusion: bool = False, fov=None, sensing: Optional[Sensing] = None):
+                 occlusion: bool = False, fov=None, sensing: Optional[Sensing] = None, bodies: bool = False):
         what = "SensorRolloutEngine"
         if sensing is None:
             sensing = Sensing.of(env, what, occlusion=occlusion, fov=fov)
+        bodies = bodies_option(env, what, bodies)
         if sensor is None and sensing is not None:
             sensor = sensing.model(float(env.params["comm_radius"]))
+        if sensor is None and bodies:
+            sensor = _identity_sensor
         if not callable(sensor):
             raise ValueError("SensorRolloutEngine: sensor must be a callable (alpha, t) -> alpha_obs")
         self._need_actor(what, actor, mode)
         super().__init__(what, sensing, False, env, n_env, T, device, env_offset, actor, mode, init_state)
-        self.sensor = sensor
+        self.sensor, self.bodies = sensor, bodies
 
     def _observe(self, t: int):
         env, n = self.env, self.env.num_agents
         agent = self.buf.states[t][:, :n]
         goal = self.buf.states[t][:, n:n + env.num_goals]
-        alpha_obs = self.sensor(env.lidar_scan(agent, self.obstacles), t)
+        scan = env.lidar_scan(agent, self.obstacles, bodies=True) if self.bodies else env.lidar_scan(agent, self.obstacles)
+        alpha_obs = self.sensor(scan, t)
         seen = env.get_graph((agent, goal, self.obstacles), out=self._observed_at(t),
                              lidar_data=env.lidar_hits(agent, alpha_obs))
         if self.occlusion or self.fov is not None:
@@ -364,18 +373,21 @@ class NoisyLidarRolloutEngine(_ObservedRolloutEngine):
     draw at row env_offset + b.  occlusion: env.observe(..., occlusion=True), the agents hidden from each other by
     obstacles dropped from every observed graph in the same launch.  fov: env.observe(..., fov=deg), the senders outside
     the receiver's camera cone dropped as well (the envs with a heading; None and 180: no cone).  sensing: a
-    utils.sensor.Sensing in place of the four keywords.
+    utils.sensor.Sensing in place of the four keywords.  bodies: env.observe(..., bodies=True), the beams returning off
+    the other agents' bodies too.
 
     `run` returns the true Rollout; `observed_rollout()` the Rollout the algorithms train on: graph and next_graph
     the observed ones, every other field the true run's."""
 
     def __init__(self, env: MultiAgentEnv, n_env: int, T: Optional[int] = None, device=None, env_offset: int = 0,
                  actor=None, mode: int = RolloutEngine.MODE_SAMPLE, sigma: float = 0.0, dropout: float = 0.0,
-                 init_state=None, occlusion: bool = False, fov=None, sensing: Optional[Sensing] = None):
+                 init_state=None, occlusion: bool = False, fov=None, sensing: Optional[Sensing] = None,
+                 bodies: bool = False):
         what = "NoisyLidarRolloutEngine"
         self._need_actor(what, actor, mode)
         if sensing is None:
             sensing = Sensing.of(env, what, sigma, dropout, occlusion, fov)
+        self.bodies = bodies_option(env, what, bodies)
         super().__init__(what, sensing, True, env, n_env, T, device, env_offset, actor, mode, init_state)
         self.sigma, self.dropout = sensing.sigma or 0.0, sensing.dropout or 0.0
 
@@ -384,7 +396,7 @@ class NoisyLidarRolloutEngine(_ObservedRolloutEngine):
         s = self.buf.states[t]
         env.observe((s[:, :n], s[:, n:n + env.num_goals], self.obstacles), t, sigma=self.sigma, dropout=self.dropout,
                     seed=self.key, env_offset=self.env_offset, out=self._observed_at(t), occlusion=self.occlusion,
-                    fov=self.fov)
+                    fov=self.fov, **({"bodies": True} if self.bodies else {}))
 
     def _run(self):
         super()._run()

@@ -67,11 +67,11 @@ class Trainer:
         """test_rollout with the deterministic policy on n_env_test envs (trainer.py:85-116)."""
         assert self.n_env_test <= 1_000, "n_env_test must be less than or equal to 1_000"
         if self._test_engine is None:
-            sensing = getattr(self.algo, "sensing", None)
-            if sensing is not None:  # trained under a sensor model: the true costs under sensed control
+            sensing, bodies = getattr(self.algo, "sensing", None), getattr(self.algo, "bodies", False)
+            if sensing is not None or bodies:  # trained under a sensor model: the true costs under sensed control
                 self._test_engine = NoisyLidarRolloutEngine(
                     self.env_test, self.n_env_test, self.env_test.max_episode_steps, self.algo.device,
-                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sensing=sensing)
+                    actor=self.algo.actor, mode=RolloutEngine.MODE_DET, sensing=sensing, bodies=bodies)
             else:
                 self._test_engine = RolloutEngine(self.env_test, self.n_env_test, self.env_test.max_episode_steps,
                                                   self.algo.device, actor=self.algo.actor, mode=RolloutEngine.MODE_DET)

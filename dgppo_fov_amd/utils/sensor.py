@@ -90,6 +90,20 @@ def cone_angle(env, what: str, fov) -> Optional[float]:
     return None if deg == 180.0 else deg
 
 
+def bodies_option(env, what: str, bodies, algo_cls=None) -> bool:
+    """The `bodies` option (the LiDAR's beams also return off the other agents' bodies), validated: False for a false
+    value; a true one needs an algorithm that does not read the true state off the rollout's graphs (`algo_cls` with
+    SENSOR_OK) and a LiDAR env with obstacles, because the hit rows exist only there.  ValueError, or
+    NotImplementedError for the VMAS envs, before the GPU is touched.  It travels beside the Sensing record."""
+    if not bodies:
+        return False
+    if algo_cls is not None and not algo_cls.SENSOR_OK:
+        raise ValueError(f"{algo_cls.__name__} evaluates env.get_cost on the rollout's graphs, which must be the true "
+                         "ones: lidar_bodies is not supported (dgppo, informarl, informarl_lagr are)")
+    env._require_lidar(what)
+    return True
+
+
 @dataclass(frozen=True)
 class Sensing:
     """What stands between the world and the policy, validated once: range noise `sigma` (world units) and beam

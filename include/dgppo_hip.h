@@ -364,6 +364,30 @@ int dgppo_agent_fov(const dgppo_env_cfg* cfg, const dgppo_agent_fov_io* io, void
 int dgppo_lidar_observe_fov(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, float half_angle_deg,
                             void* stream);
 
+/* LiDAR sees agents: a beam also returns off the other agents' bodies, discs of radius car_radius.  For receiver i,
+ * beam (dx, dy) = ray_dirs[r] from (sx, sy) = columns 0, 1 of agent row i, rho = car_radius, and every other agent
+ * j != i in increasing j with (cx, cy) = columns 0, 1 of row j -- fp32, contraction off, in this order:
+ *   mx = cx - sx; my = cy - sy; cc = (mx mx + my my) - rho rho; aa = dx dx + dy dy; bb = dx mx + dy my
+ *   disc = bb bb - aa cc
+ *   t_j = 0                          if cc <= 0                 (the start is inside or on body j)
+ *       = t = (bb - sqrt(disc)) / aa if bb > 0 and disc >= 0 and 0 <= t <= 1
+ *       = 1e6                        otherwise                  (every comparison is false on NaN)
+ *   a_body = min_j t_j (1e6 when n == 1);  alpha = a_obs if a_obs is NaN, else a_body if a_body < a_obs, else a_obs
+ * with a_obs dgppo_lidar_scan's value.  A NaN or infinite row gives no body return and never a NaN t_j; a wall nearer
+ * than a body hides it.  Agents still do not cut lines of sight (dgppo_lidar_sight is unchanged), and the env step,
+ * reward and cost keep the obstacle-only scan.
+ *
+ * dgppo_lidar_scan_bodies: dgppo_lidar_scan with that alpha; same io, same refusals.
+ *
+ * dgppo_lidar_observe_bodies: dgppo_lidar_observe_fov that also accepts DGPPO_OBSERVE_BODIES in `flags`: the beams'
+ * alphas are the ones above before the sensor model, so a body return gets noise and dropout, is ranked among the
+ * agent's beams and becomes a hit row like any other.  Without the bit the entry is dgppo_lidar_observe_fov.  The other
+ * three entries keep refusing the bit.  No ABI number change (new symbols only). */
+#define DGPPO_OBSERVE_BODIES 16
+int dgppo_lidar_scan_bodies(const dgppo_env_cfg* cfg, const dgppo_lidar_scan_io* io, void* stream);
+int dgppo_lidar_observe_bodies(const dgppo_env_cfg* cfg, const dgppo_lidar_observe_io* io, float half_angle_deg,
+                               void* stream);
+
 /* Host-side helper: `count` obstacle records (count x 16, DGPPO_OBST_FIELDS layout) from HOST arrays center
  * (count x 2), width, height, theta (count each) = Rectangle.create (dgppo/env/obstacle.py:39-56) with the fp32
  * sin / cos and operation order of the reset kernels, so a scene can be assembled without a GPU. */

@@ -36,7 +36,9 @@ names both values.  `--lidar-occlusion` (same envs, with or without the noise fl
 drops every agent-agent edge whose receiver has no line of sight to its sender past the obstacles from the graphs the
 policy sees (env.line_of_sight, utils/sensor.py mask_unseen).  `--lidar-fov DEG` (LidarBicycleTarget and
 LidarOmniTarget, no config.yaml entry needed, combines with the other three) drops every agent-agent edge whose sender is
-outside the receiver's forward cone of half angle DEG (env.field_of_view)."""
+outside the receiver's forward cone of half angle DEG (env.field_of_view).  `--lidar-bodies` (Lidar envs with
+obstacles, no config.yaml entry needed, combines with the other four) lets the beams return off the other agents'
+bodies as well (env.lidar_scan(bodies=True)): a robot whose edge is hidden still shows up as an anonymous hit row."""
 import argparse
 import os
 
@@ -90,6 +92,15 @@ def test(args):
                                  args.lidar_occlusion, args.lidar_fov)
         except (ValueError, NotImplementedError) as e:
             raise SystemExit(str(e))
+    else:
+        sensing = None
+    if args.lidar_bodies:  # likewise
+        from dgppo_fov_amd.utils.sensor import bodies_option
+
+        try:
+            bodies_option(env, "--lidar-bodies", True)
+        except (ValueError, NotImplementedError) as e:
+            raise SystemExit(str(e))
     if args.cbf is not None and args.video and not args.no_video:  # refused before anything is loaded or run
         if not callable(getattr(algo, "get_Vh", None)):
             raise SystemExit(f"--cbf needs an algorithm with get_Vh; {cfg['algo']} has none")
@@ -122,12 +133,13 @@ def test(args):
     if scene is not None:  # episodes are rows [offset:epi] of the file
         cut = lambda t: None if t is None else t[args.offset:args.epi]  # noqa: E731
         init_state = type(scene)(*(cut(part) for part in scene))
-    if sensed:
+    if sensed or args.lidar_bodies:
         from dgppo_fov_amd.trainer.rollout import SensorRolloutEngine
 
-        sensor = sensing.model(float(env.params["comm_radius"]), seed=args.seed)
+        sensor = sensing.model(float(env.params["comm_radius"]), seed=args.seed) if sensing is not None else None
         eng = SensorRolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset,
-                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state, sensing=sensing)
+                                  actor=algo.actor, mode=mode, sensor=sensor, init_state=init_state, sensing=sensing,
+                                  bodies=args.lidar_bodies)
     else:
         eng = RolloutEngine(env, len(episodes), env.max_episode_steps, dev, env_offset=args.offset, actor=algo.actor,
                             mode=mode, init_state=init_state)
@@ -148,7 +160,8 @@ def test(args):
           f"cost: {np.mean(costs):.3f}, min/max cost: {np.min(costs):.3f}/{np.max(costs):.3f}, "
           f"safe_rate: {safe_mean * 100:.3f}%" + (f", lidar noise: {sigma:g}, lidar dropout: {drop:g}" if sensed else "") +
           (", lidar occlusion: on" if args.lidar_occlusion else "") +
-          (f", lidar fov: {args.lidar_fov:g}" if args.lidar_fov is not None else ""))
+          (f", lidar fov: {args.lidar_fov:g}" if args.lidar_fov is not None else "") +
+          (", lidar bodies: on" if args.lidar_bodies else ""))
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(f"{env.num_agents},{args.epi},{env.max_episode_steps},{env.area_size},{env.params['n_obs']},"
@@ -204,6 +217,7 @@ def build_parser():
     parser.add_argument("--lidar-dropout", type=float, default=None, metavar="P")
     parser.add_argument("--lidar-occlusion", action="store_true", default=False)  # obstacles hide agents from each other
     parser.add_argument("--lidar-fov", type=float, default=None, metavar="DEG")  # half angle of the camera cone
+    parser.add_argument("--lidar-bodies", action="store_true", default=False)  # beams return off the other agents too
     return parser
 
 

@@ -14,7 +14,9 @@ whose receiver has no line of sight to its sender is dropped from every graph th
 (LidarBicycleTarget and LidarOmniTarget, same algorithms, combines with the other three) gives every robot a forward
 camera cone of half angle DEG for neighbour sensing: an agent-agent edge whose sender is outside the receiver's cone is
 dropped as well (the LiDAR beams stay omnidirectional); at the env's own `fov_angle_deg` the sensed cone is the
-constrained one bit for bit."""
+constrained one bit for bit.  `--lidar-bodies` (Lidar envs with obstacles, same algorithms, combines with the other
+four) lets the LiDAR beams return off the other agents' bodies as well, so a robot whose edge is hidden still shows up
+in the observed graphs as an anonymous hit row; the env steps, rewards and costs keep the obstacle-only scan."""
 import argparse
 import datetime
 import json
@@ -45,6 +47,8 @@ def check_resume_args(args, log_dir, world=None):
         saved.setdefault("lidar_occlusion", False)  # runs saved before the flag existed trained without it
     if cur.get("lidar_fov") is not None:
         saved.setdefault("lidar_fov", None)  # likewise
+    if cur.get("lidar_bodies"):
+        saved.setdefault("lidar_bodies", False)  # likewise
     diff = {k: (saved[k], cur.get(k)) for k in saved if k not in RESUME_FREE and saved[k] != cur.get(k)}
     if diff:
         raise SystemExit("--resume: flags differ from the run's own (saved, given): " +
@@ -97,7 +101,7 @@ def train(args):
         lagr_init=args.lagr_init, lr_lagr=args.lr_lagr, train_steps=args.steps,
         cbf_schedule=not args.no_cbf_schedule, cost_schedule=args.cost_schedule, device=device,
         lidar_noise=args.lidar_noise, lidar_dropout=args.lidar_dropout, lidar_occlusion=args.lidar_occlusion,
-        lidar_fov=args.lidar_fov)
+        lidar_fov=args.lidar_fov, lidar_bodies=args.lidar_bodies)
     if args.load_checkpoint:
         print(f"> Loading checkpoint from {args.load_checkpoint}, step {args.load_step}")
         algo.load(args.load_checkpoint, args.load_step)
@@ -193,6 +197,8 @@ def build_parser():
                         help="obstacles hide agents from each other in the graphs the networks see")
     parser.add_argument("--lidar-fov", type=float, default=None, metavar="DEG",
                         help="half angle of the camera cone: agents outside it are hidden from the receiver")
+    parser.add_argument("--lidar-bodies", action="store_true", default=False,
+                        help="LiDAR beams also return off the other agents' bodies in the graphs the networks see")
     return parser
 
 
